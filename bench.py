@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """CRIS-R50 train-step throughput on MI355X (BASELINE.json metric: train-step samples/sec, CRIS-R50 416x416).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds what takes runs of its own or
+reads the machine: the per-kernel HIP-event pass (`roofline`, `kernels`, --shape-table), the drop-in module runs
+(`module_path`), the CPU baseline (`cpu_baseline`) and the rocm-smi clock / power readings (`gpu_state_*`).
+--dump-outputs DIR: the last timed step's results as DIR/*.npy (dump_outputs).
 
 N > 1: one rank per GPU.  Started under torch.distributed.run (RANK / WORLD_SIZE in the environment) the process IS a rank;
 started plainly (`python bench.py --gpus 8`, no WORLD_SIZE) it re-launches itself under torch.distributed.run with N ranks on
@@ -164,6 +169,32 @@ def cpu_baseline(spec, batch, size, word_len, physical):
             "train_step_s_by_threads": {str(k): v for k, v in trains.items()}, "train_step_s_median": med, "train_step_s_runs": best_runs,
             "eval_forward_bs1_ms": evals[be], "eval_forward_bs1_threads": be,
             "eval_forward_bs1_ms_by_threads": {str(k): v for k, v in evals.items()}}
+
+
+DUMP_STATE_SAMPLE = 1 << 22        # parameter / BatchNorm-statistic values written by --dump-outputs (16 MB as float32)
+
+
+def dump_outputs(out_dir, tr, loss, metric):
+    """--dump-outputs: what the last timed step computed, for comparing two builds output for output - the loss and train
+    metric its caller receives (loss.npy, metric.npy) and the parameters and BatchNorm running statistics the step left
+    behind.  Those are ~100 M values, so state_sample.npy holds a fixed sample: per tensor (state_dict order) a seeded
+    choice of indices proportional to its size, at least 256 or all of it, the same indices in every run of a
+    configuration."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "metric.npy"), metric.detach().float().cpu().numpy())
+    e = tr.engine
+    state = [t for t in list(e.P.values()) + list(e.Bf.values()) if t.is_floating_point()]
+    frac = min(1.0, DUMP_STATE_SAMPLE / sum(t.numel() for t in state))
+    g = torch.Generator().manual_seed(0)
+    parts = []
+    for t in state:
+        n = t.numel()
+        k = min(n, max(256, int(n * frac)))
+        idx = torch.arange(n) if k == n else torch.randint(0, n, (k,), generator=g).sort().values
+        parts.append(t.detach().reshape(-1)[idx.to(t.device)].float().cpu())
+    np.save(os.path.join(out_dir, "state_sample.npy"), torch.cat(parts).numpy())
 
 
 def spawn_ranks(n):
@@ -420,7 +451,19 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="exercise only the multi-rank launch protocol (spawn, rendezvous, barrier, max-over-ranks, one JSON "
                          "line from rank 0) without touching a GPU - what tests/test_bench_launch.py runs on the CPU")
+    ap.add_argument("--full", action="store_true",
+                    help="native path: after the timed steps also run the per-kernel timing pass, the drop-in module runs and the CPU "
+                         "baseline, and read the GPU's clocks (each can still be left out with its --no-... option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="native path: write the last timed step's loss, train metric and a fixed sample of the updated parameters "
+                         "and BatchNorm statistics as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.shape_table and not args.full:
+        ap.error("--shape-table comes from the per-kernel timing pass: add --full")
+    if args.dump_outputs and args.path != "native":
+        ap.error("--dump-outputs: native path only")
 
     if args.grad_exchange is not None:
         os.environ["CRIS_GRAD_EXCHANGE"] = args.grad_exchange
@@ -471,7 +514,7 @@ def main():
     word_len = args.word_len if args.word_len is not None else (22 if args.size == 480 else head.word_len)
     head = dataclasses.replace(head, word_len=word_len)
     sd = arch.synthetic_state_dict(clip, head, 0)
-    smi0 = gpu_state(local) if rank == 0 else None
+    smi0 = gpu_state(local) if rank == 0 and args.full else None
     tr = NativeTrainer(clip, head, sd, dev, comm=comm, sync_bn=world > 1, use_graph=not args.no_graph, launch=args.launch)
     del sd
     nb = 4
@@ -494,15 +537,17 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss, _ = tr.train_step(*batches[i % nb])
+        loss, metric = tr.train_step(*batches[i % nb])
     sync()
     dt = time.perf_counter() - t0
     loss_v = float(loss)
-    smi1 = gpu_state(local) if rank == 0 else None
+    if args.dump_outputs and rank == 0:          # (before anything else steps the trainer)
+        dump_outputs(args.dump_outputs, tr, loss, metric)
+    smi1 = gpu_state(local) if rank == 0 and args.full else None
     # per-kernel HIP-event timing needs individual launches: an extra instrumented EAGER pass right after the timed
     # region (the timed region itself replays the captured HIP graph - one host call per step)
     timer, timer_steps = None, 0
-    if not args.no_kernel_timer:                 # every rank runs the pass (its collectives must match across ranks)
+    if args.full and not args.no_kernel_timer:   # every rank runs the pass (its collectives must match across ranks)
         timer = ops.KernelTimer()
         ops.KERNEL_TIMER = timer
         timer_steps = min(3, args.steps)
@@ -593,7 +638,7 @@ def main():
                     f.write("%s\t%s\t%.1f\t%.3f\t%.1f\t%.1f\t%.0f\n" % (
                         kn, tag, v["launches"] / timer_steps, v["ms"] / timer_steps, 1e3 * v["ms"] / v["launches"],
                         v["flops"] / (v["ms"] * 1e-3) / 1e12, v["bytes"] / (v["ms"] * 1e-3) / 1e9))
-        if world == 1 and not args.no_module_path and args.spec == "r50":
+        if args.full and world == 1 and not args.no_module_path and args.spec == "r50":
             # the path the north star names - build_segmenter -> optimizer -> GradScaler under the reference's loop body - in the
             # same record (round-4 review: "neither number is in a driver record"): the unchanged loop, the one-line optimizer
             # swap, and both again under the one-rank DistributedDataParallel wrap the reference's train.py always builds
@@ -621,7 +666,7 @@ def main():
                           "trainMetricGPU + three .item() syncs), %d timed steps each, same batch shape as the native line" % args.module_steps)
             out["module_path"] = mp
             out["module_path_rc"] = mp["module_path_rc"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.spec, args.batch, args.size, head.word_len, physical_cores())
         emit_line(out)
     if world > 1:

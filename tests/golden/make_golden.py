@@ -8,7 +8,9 @@ train-mode forward + backward (dropout 0 - torch's Philox dropout stream cannot 
 other implementation) and eval-mode forward on seeded synthetic batches, and stores the results as
 small .npz fixtures next to this script.  tests/test_oracle_golden.py pins oracle/cris_oracle.py
 against them; the GPU parity tests then compare the HIP path with the oracle and with these files.
-Fixtures hold outputs only (weights/inputs are regenerated from seeds on any machine).
+Fixtures hold outputs only (weights/inputs are regenerated from seeds on any machine), except
+clip_bpe_merges.txt.gz: the part of the reference's CLIP merge list that both tokenizers read.
+One group only: `make_golden.py tokenizer_reference | ref_loop | train_metric | <case name>`.
 """
 import dataclasses
 import json
@@ -110,6 +112,119 @@ def tokenizer_vectors():
     print("tokenizer vectors", len(out))
 
 
+def merge_list():
+    """clip_bpe_merges.txt.gz: the version header and the first 48894 merges of the reference's
+    utils/bpe_simple_vocab_16e6.txt.gz - all that its tokenizer and cris.pytorch_amd.tokenizer read of it."""
+    import gzip
+    from cris.pytorch_amd import tokenizer as T
+    with gzip.open(os.path.join(ref_harness.REF_ROOT, "utils", "bpe_simple_vocab_16e6.txt.gz"), "rb") as f:
+        lines = f.read().decode("utf-8").split("\n")
+    data = ("\n".join(lines[:1 + T.N_MERGES]) + "\n").encode("utf-8")
+    with open(os.path.join(HERE, "clip_bpe_merges.txt.gz"), "wb") as f:
+        f.write(gzip.compress(data, mtime=0))
+    print("merge list", T.N_MERGES)
+
+
+WORDS = ("the man in red shirt on left woman's umbrella giraffe's head 2nd from right guy w/ hat it's they're don't i'll we've i'm she'd "
+         "skateboarder blue-ish jacket #3 person (partially hidden) behind bench... zebra closest 2 us pizza w/o pepperoni ??? ok "
+         "Bus 42 A&W logo 100% café naïve über señor 東京 ÅNGSTRÖM ﬁne x² ½ cup").split()
+
+
+def _sentences(n, seed):
+    import random
+    rng = random.Random(seed)
+    out = []
+    for _ in range(n):
+        k = rng.randint(1, 24)
+        parts = [rng.choice(WORDS) for _ in range(k)]
+        sep = rng.choice([" ", " ", "  ", " \t", "\n"])
+        s = sep.join(parts)
+        if rng.random() < 0.2:
+            s = "  " + s.upper() + " "
+        if rng.random() < 0.15:
+            s = s.replace("&", "&amp;").replace("w/", "w&#47;")
+        if rng.random() < 0.1:
+            s += " " + "".join(rng.choice("abcdefghijklmnopqrstuvwxyz0123456789'-") for _ in range(rng.randint(1, 30)))
+        out.append(s)
+    return out
+
+
+def tokenizer_reference():
+    """tokenizer_reference.json.gz: the reference tokenizer's answers (utils/dataset.py tokenize with the ftfy stub,
+    utils/simple_tokenizer.py encode / decode) for tests/test_tokenizer.py - token ids at context lengths 17 / 22 / 77 of 3000
+    seeded referring-expression sentences and edge cases, its error on an over-long text, encode / decode of the first 300
+    texts, and 400 arbitrary unicode texts (control characters included, surrogates excluded) drawn by hypothesis
+    (derandomized) at context lengths 8 / 17 / 22 / 77."""
+    import gzip
+    from hypothesis import given, settings, strategies as st
+    ref_harness.import_reference()
+    from utils import dataset
+    texts = _sentences(3000, 0) + ["", " ", "a", "<|startoftext|> hi <|endoftext|>", "it's", "'s", "''''", "x" * 200, "1234567890",
+                                    "&amp;amp; &lt;b&gt;", "tab\there", "émigré's café"]
+    out = {"texts": texts, "ids": {}}
+    for L in (17, 22, 77):
+        ids = dataset.tokenize(texts, L, True)
+        out["dtype"] = str(ids.dtype)
+        out["ids"][str(L)] = ids.tolist()
+    try:
+        dataset.tokenize("x " * 40, 17, False)
+        raise AssertionError("the reference accepted an over-long text")
+    except RuntimeError as ex:
+        out["too_long_error"] = str(ex)
+    ref_tok = dataset._tokenizer
+    out["encode"] = [ref_tok.encode(t) for t in texts[:300]]
+    out["decode"] = [ref_tok.decode(ids) for ids in out["encode"]]
+    cases = []
+
+    @settings(max_examples=400, deadline=None, derandomize=True, database=None)
+    @given(st.text(alphabet=st.characters(blacklist_categories=("Cs",)), max_size=60), st.sampled_from([8, 17, 22, 77]))
+    def draw(text, L):
+        cases.append({"text": text, "L": L, "ids": dataset.tokenize(text, L, True)[0].tolist()})
+
+    draw()
+    out["hypothesis"] = cases
+    with open(os.path.join(HERE, "tokenizer_reference.json.gz"), "wb") as f:
+        f.write(gzip.compress(json.dumps(out, ensure_ascii=True).encode(), mtime=0))
+    print("tokenizer reference", len(texts), "texts,", len(cases), "hypothesis cases")
+
+
+def ref_loop_reference():
+    """ref_loop_reference.npz: the reference's own engine.engine.train (logging stubbed) over the cases of
+    tests/test_ref_loop_cpu.py - parameters and BatchNorm buffers afterwards per max_norm, computed with that file's pinned CPU
+    kernels in a process of their own - and its trainMetricGPU on that file's seeded metric cases."""
+    import subprocess
+    import time
+    import types
+    from types import SimpleNamespace as NS
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_ref_loop_cpu as C
+    if any(os.environ.get(k) != v for k, v in C.PINNED_ENV.items()):
+        subprocess.run([sys.executable, os.path.abspath(__file__), "ref_loop"], env=dict(os.environ, **C.PINNED_ENV), check=True)
+        return
+    ref_harness.import_reference()
+    if "tqdm" not in sys.modules:
+        m = types.ModuleType("tqdm")
+        m.tqdm = lambda x, *a, **k: x
+        sys.modules["tqdm"] = m
+    sys.modules["wandb"].log = lambda *a, **k: None
+    import engine.engine as ref_engine           # the reference's engine/engine.py
+    from utils.misc import trainMetricGPU
+
+    def train(batches, model, opt, sched, scaler, max_norm):
+        ref_engine.train(batches, model, opt, sched, scaler, 0, NS(epochs=1, max_norm=max_norm, print_freq=10 ** 9))
+
+    cuda, sleep = torch.Tensor.cuda, time.sleep
+    torch.Tensor.cuda = lambda self, *a, **k: self                # CPU run of a loop written for cuda
+    time.sleep = lambda s: None                                   # engine/engine.py:30
+    try:
+        out = C.pinned_states(train)
+    finally:
+        torch.Tensor.cuda, time.sleep = cuda, sleep
+    out["metric"] = np.array([[float(v) for v in trainMetricGPU(x.clone(), t)] for x, t in C.metric_cases()], dtype=np.float64)
+    np.savez_compressed(os.path.join(HERE, "ref_loop_reference.npz"), **out)
+    print("ref loop reference", len(out), "arrays")
+
+
 def metric_vectors():
     """Known answers of the reference's train metric (utils/misc.py:114-129 trainMetricGPU) on seeded logits / masks,
     including logits exactly at the 0.35 threshold and empty masks (union 0 -> IoU 0 through the +1e-6)."""
@@ -150,6 +265,11 @@ if __name__ == "__main__":
     if not sys.argv[1:]:
         key_listing()
         tokenizer_vectors()
+    if not sys.argv[1:] or "tokenizer_reference" in sys.argv[1:]:
+        merge_list()
+        tokenizer_reference()
+    if not sys.argv[1:] or "ref_loop" in sys.argv[1:]:
+        ref_loop_reference()
     if not sys.argv[1:] or "train_metric" in sys.argv[1:]:
         metric_vectors()
     only = sys.argv[1:]

@@ -1,26 +1,28 @@
-"""The loop restatement of tests/ref_loop.py is pinned to the reference: the reference's OWN `engine.engine.train` (imported
-from /root/reference with its logging dependencies stubbed) and `ref_loop.train_steps` drive two copies of one small CPU
-model over the same batches with the same Adam / MultiStepLR / GradScaler objects; parameters and BatchNorm buffers must be
-bit-identical afterwards, and trainMetricGPU must agree on random inputs.  Skipped where the reference is absent (GPU box)."""
-import copy
+"""The loop restatement of tests/ref_loop.py is pinned to the reference: the reference's OWN `engine.engine.train` drove one small
+CPU model over the batches of loop_case() with the Adam / MultiStepLR / GradScaler objects built there, and its parameters and
+BatchNorm buffers afterwards are stored in tests/golden/ref_loop_reference.npz (tests/golden/make_golden.py ref_loop).
+`ref_loop.train_steps` on the same case must reproduce them bit for bit, and trainMetricGPU's stored answers on random inputs
+exactly."""
 import os
+import subprocess
 import sys
-import time
-import types
-from types import SimpleNamespace as NS
+import tempfile
 
+import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
 from torch import nn
 
 from conftest import GOLDEN
+import ref_loop
 
-sys.path.insert(0, GOLDEN)
-import ref_harness  # noqa: E402
-import ref_loop  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not ref_harness.reference_available(), reason="reference not present")
+MAX_NORMS = (0.0, 0.5)
+# Bit for bit on any x86 host: with torch's default CPU kernels the last bits of these parameters differ between hosts (the
+# vector width and oneDNN / MKL code paths follow the CPU model).  Both loops therefore run in a process of their own - torch
+# fixes its kernel choice at the first call - with ATen's scalar kernels, oneDNN off, MKL in its conditional numerical
+# reproducibility mode and one thread (pinned_states).
+PINNED_ENV = {"ATEN_CPU_CAPABILITY": "default", "MKL_CBWR": "COMPATIBLE", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
 
 
 class _Toy(nn.Module):
@@ -43,65 +45,85 @@ class _Toy(nn.Module):
         return pred.detach()
 
 
-def _reference_train():
-    ref_harness.import_reference()
-    for name in ("tqdm",):
-        if name not in sys.modules:
-            m = types.ModuleType(name)
-            m.tqdm = lambda x, *a, **k: x
-            sys.modules[name] = m
-    wb = sys.modules["wandb"]
-    wb.log = lambda *a, **k: None
-    import engine.engine as ref_engine           # the reference's engine/engine.py
-    return ref_engine
-
-
-@pytest.fixture(scope="module")
-def pg():
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", "29533")
-    if not dist.is_initialized():
-        dist.init_process_group("gloo", rank=0, world_size=1)
-    yield
-    dist.destroy_process_group()
-
-
-def test_train_metric_matches_reference():
-    ref_harness.import_reference()
-    from utils.misc import trainMetricGPU
-    g = torch.Generator().manual_seed(0)
-    for _ in range(5):
-        x = torch.randn(4, 1, 16, 16, generator=g) * 2
-        t = (torch.rand(4, 1, 16, 16, generator=g) > 0.6).float()
-        a = trainMetricGPU(x.clone(), t)
-        b = ref_loop.train_metric_gpu(x.clone(), t)
-        assert float(a[0]) == float(b[0]) and float(a[1]) == float(b[1])
-
-
-@pytest.mark.parametrize("max_norm", [0.0, 0.5])
-def test_restated_loop_equals_reference_engine_train(pg, monkeypatch, max_norm):
-    ref_engine = _reference_train()
-    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)        # CPU run of a loop written for cuda
-    monkeypatch.setattr(time, "sleep", lambda s: None)                             # engine/engine.py:30
+def loop_case():
+    """(batches, freshly seeded model, (optimizer, scheduler, scaler)) - what both loops are driven with"""
     g = torch.Generator().manual_seed(1)
     batches = [(torch.randn(4, 3, 32, 32, generator=g), torch.randint(0, 50, (4, 5), generator=g),
                 (torch.rand(4, 32, 32, generator=g) > 0.5).float()) for _ in range(5)]
     torch.manual_seed(0)
-    m_ref = _Toy()
-    m_own = copy.deepcopy(m_ref)
+    m = _Toy()
+    groups = [{"params": [p for n, p in m.named_parameters() if n.startswith("conv")], "initial_lr": 1e-3},
+              {"params": [p for n, p in m.named_parameters() if not n.startswith("conv")], "initial_lr": 1e-2}]
+    # (fused: the update's square root in torch's own kernel - the per-tensor Adam hands it to MKL's vector math, whose last bit
+    # follows the CPU model whatever MKL_CBWR says)
+    opt = torch.optim.Adam(groups, lr=1e-2, weight_decay=0.0, fused=True)
+    sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=[35], gamma=0.1)
+    return batches, m, (opt, sched, torch.amp.GradScaler("cuda", enabled=False))
 
-    def setup(m):
-        groups = [{"params": [p for n, p in m.named_parameters() if n.startswith("conv")], "initial_lr": 1e-3},
-                  {"params": [p for n, p in m.named_parameters() if not n.startswith("conv")], "initial_lr": 1e-2}]
-        opt = torch.optim.Adam(groups, lr=1e-2, weight_decay=0.0)
-        sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=[35], gamma=0.1)
-        return opt, sched, torch.amp.GradScaler("cuda", enabled=False)
 
-    opt, sched, scaler = setup(m_ref)
-    args = NS(epochs=1, max_norm=max_norm, print_freq=10 ** 9)
-    ref_engine.train(batches, m_ref, opt, sched, scaler, 0, args)
-    opt2, _, scaler2 = setup(m_own)
-    res = ref_loop.train_steps(batches, m_own, opt2, scaler2, max_norm=max_norm, device_type="cpu")
+def metric_cases():
+    g = torch.Generator().manual_seed(0)
+    out = []
+    for _ in range(5):
+        x = torch.randn(4, 1, 16, 16, generator=g) * 2
+        t = (torch.rand(4, 1, 16, 16, generator=g) > 0.6).float()
+        out.append((x, t))
+    return out
+
+
+def pinned_states(train):
+    """{"<max_norm>/<state_dict key>": array} after `train(batches, model, optimizer, scheduler, scaler, max_norm)` ran each case
+    of loop_case() on one gloo rank; call in a process started with PINNED_ENV"""
+    assert all(os.environ.get(k) == v for k, v in PINNED_ENV.items()), "start the process with PINNED_ENV"
+    torch.backends.mkldnn.enabled = False
+    torch.set_num_threads(1)
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        dist.init_process_group("gloo", init_method="file://" + os.path.join(td, "pg"), rank=0, world_size=1)
+        try:
+            for max_norm in MAX_NORMS:
+                batches, model, (opt, sched, scaler) = loop_case()
+                train(batches, model, opt, sched, scaler, max_norm)
+                out.update({"%g/%s" % (max_norm, k): v.numpy() for k, v in model.state_dict().items()})
+        finally:
+            dist.destroy_process_group()
+    return out
+
+
+def _restated_train(batches, model, opt, sched, scaler, max_norm):
+    res = ref_loop.train_steps(batches, model, opt, scaler, max_norm=max_norm, device_type="cpu")
     assert len(res) == len(batches)
-    for (k, a), (_, b) in zip(m_ref.state_dict().items(), m_own.state_dict().items()):
-        assert torch.equal(a, b), k
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(os.path.join(GOLDEN, "ref_loop_reference.npz"))
+
+
+@pytest.fixture(scope="module")
+def restated():
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "states.npz")
+        cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [os.path.abspath(__file__), out]
+        r = subprocess.run(cmd, env=dict(os.environ, **PINNED_ENV), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stdout[-3000:]
+        return dict(np.load(out))
+
+
+def test_train_metric_matches_reference(golden):
+    for (x, t), (iou, pr5) in zip(metric_cases(), golden["metric"]):
+        b = ref_loop.train_metric_gpu(x.clone(), t)
+        assert float(b[0]) == iou and float(b[1]) == pr5
+
+
+@pytest.mark.parametrize("max_norm", MAX_NORMS)
+def test_restated_loop_equals_reference_engine_train(golden, restated, max_norm):
+    keys = sorted(k for k in restated if k.startswith("%g/" % max_norm))
+    assert keys and keys == sorted(k for k in golden.files if k.startswith("%g/" % max_norm))
+    for k in keys:
+        assert torch.equal(torch.from_numpy(restated[k]), torch.from_numpy(golden[k])), k
+
+
+if __name__ == "__main__":                       # the `restated` fixture's process
+    np.savez(sys.argv[1], **pinned_states(_restated_train))

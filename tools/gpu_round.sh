@@ -17,7 +17,7 @@ if [[ "$what" == all || "$what" == *stage* ]]; then
   timeout 300 python tools/stage_bwd_check.py tiny 4 64 > $O/stage_bwd_tiny.log 2>&1; grep -v Warning $O/stage_bwd_tiny.log | tail -40
 fi
 if [[ "$what" == all || "$what" == *bench* ]]; then
-  timeout 600 python bench.py --steps 10 --warmup 3 > $O/bench.log 2>&1; echo "bench rc=$?"; tail -3 $O/bench.log
+  timeout 600 python bench.py --full --steps 10 --warmup 3 > $O/bench.log 2>&1; echo "bench rc=$?"; tail -3 $O/bench.log
 fi
 if [[ "$what" == all || "$what" == *prof* ]]; then
   rm -rf $O/prof
