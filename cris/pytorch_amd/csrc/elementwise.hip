@@ -248,6 +248,36 @@ extern "C" int cris_fill_coords(cris_bf16* x, int ldx, int coff, int nfill, int 
 }
 
 // ------------------------------------------------------------------------------------------------
+// sample gather: y[k*R + r][ycoff + c] = x[index[k]*R + r][xcoff + c]   (one image's activations -> every expression
+// of that image; index is validated by the host).  One 16-byte vector per lane, plain copies: the rows are bit-exact.
+// ------------------------------------------------------------------------------------------------
+__global__ void gather_samples_kernel(const bf16_t* __restrict__ x, int ldx, int xcoff, const int32_t* __restrict__ index,
+                                      int R, int CV, bf16_t* __restrict__ y, int ldy, int ycoff, int total) {
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+        const int cv = idx % CV;
+        const int row = idx / CV;                   // k*R + r
+        const int k = row / R;
+        const int r = row - k * R;
+        const long src = (long)index[k] * R + r;
+        const uint4 v = *reinterpret_cast<const uint4*>(x + (size_t)src * ldx + xcoff + cv * 8);
+        *reinterpret_cast<uint4*>(y + (size_t)row * ldy + ycoff + cv * 8) = v;
+    }
+}
+
+extern "C" int cris_gather_samples_bf16(const cris_bf16* x, int ldx, int xcoff, const int32_t* index, int K,
+                                        int rows_per_sample, int C, cris_bf16* y, int ldy, int ycoff, void* stream) {
+    CRIS_CHECK_ARG(x && y && index && K > 0 && rows_per_sample > 0 && C > 0, "bad args");
+    CRIS_CHECK_ARG(!(C & 7) && !(ldx & 7) && !(ldy & 7) && !(xcoff & 7) && !(ycoff & 7) && xcoff >= 0 && ycoff >= 0 &&
+                   xcoff + C <= ldx && ycoff + C <= ldy, "channels, leading dimensions and offsets: multiples of 8, slice inside the row");
+    CRIS_CHECK_ARG((long)K * rows_per_sample * ldy * 2 < (1L << 31), "output extent of 2 GiB or more");
+    const int total = K * rows_per_sample * (C / 8);
+    hipLaunchKernelGGL(gather_samples_kernel, dim3(cris_grid_1d(total, 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, xcoff,
+                       index, rows_per_sample, C / 8, y, ldy, ycoff, total);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // adds / casts
 // ------------------------------------------------------------------------------------------------
 __global__ void add_bf16_kernel(const bf16_t* a, int lda, int acoff, const bf16_t* b, int ldb, int bcoff, bf16_t* y, int ldy,

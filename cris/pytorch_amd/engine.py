@@ -803,10 +803,14 @@ class Engine:
         self.tape.append(bwd)
 
     # neck --------------------------------------------------------------------------------------
-    def _fpn(self, v3: Act, v4: Act, v5: Act, state: Act) -> Act:
+    def _fpn(self, v3: Act, v4: Act, v5: Act, state: Act, pre: Optional[dict] = None, index=None) -> Act:
+        """`pre` (inference: InferEngine.forward_multi): the image-side maps y5 / p2 / p3 that InferEngine._fpn_image computed at
+        the image batch, `index` (device int32 [K]): the image of each of the K rows of `state`.  v3 / v4 / v5 are then not read:
+        the three image-side convolutions become gathers of their outputs, everything else runs at batch K."""
         n = "neck"
         fo = self.head.fpn_out
-        B = v5.Bn
+        B = v5.Bn if pre is None else state.Bn
+        H4, W4 = (v4.H, v4.W) if pre is None else (pre["p2"].H, pre["p2"].W)
         # text projection: Linear(no bias) + BN1d + ReLU on [B, C]
         f32_head = state.t.dtype == F32
         if f32_head:
@@ -816,7 +820,10 @@ class Engine:
             s = self.bn(ys, sts, n + ".txt_proj.1")
             s32 = self.empty(B, fo[2], dtype=F32)
             ops.cast_bf16_f32(s.t, s32)
-        y5, st5 = self.gemm(v5, n + ".f1_v_proj.0.weight", fo[2], stats=True)
+        if pre is None:
+            y5, st5 = self.gemm(v5, n + ".f1_v_proj.0.weight", fo[2], stats=True)
+        else:
+            y5, st5 = self._gather(pre["y5"], index, B), None
         u = self.bn(y5, st5, n + ".f1_v_proj.1", mul=s32, want_stats=True)
         if self.training:
             if f32_head:
@@ -829,16 +836,22 @@ class Engine:
             self.tape.insert(len(self.tape) - 1, bwd_s)          # runs after the bn(mul) backward that fills dmul
         f5 = self.bn(u, u.aux["stats"], n + ".norm_layer.0")
         # fusion 2: cat[f2_v_proj(v4), up2(f5)] -> f2_cat
-        cat2 = self.new_act(v4.Bn, v4.H, v4.W, fo[1] + fo[2])
-        self.conv_bn(v4, n + ".f2_v_proj.0", n + ".f2_v_proj.1", fo[1], k=3, pad=1, out=cat2.slice(0, fo[1]))
+        cat2 = self.new_act(B, H4, W4, fo[1] + fo[2])
+        if pre is None:
+            self.conv_bn(v4, n + ".f2_v_proj.0", n + ".f2_v_proj.1", fo[1], k=3, pad=1, out=cat2.slice(0, fo[1]))
+        else:
+            self._gather(pre["p2"], index, B, out=cat2.slice(0, fo[1]))
         self._upsample(f5, cat2.slice(fo[1], fo[2]))
         # fusion 3: cat[avgpool(f3_v_proj(v3)), f4] -> f3_cat   (f4 lives in its slice of the concat buffer)
-        cat3 = self.new_act(v4.Bn, v4.H, v4.W, fo[0] + fo[1])
+        cat3 = self.new_act(B, H4, W4, fo[0] + fo[1])
         f4 = self.conv_bn(cat2, n + ".f2_cat.0", n + ".f2_cat.1", fo[1], out=cat3.slice(fo[0], fo[1]))
-        self.conv_bn(v3, n + ".f3_v_proj.0", n + ".f3_v_proj.1", fo[0], k=3, pad=1, pool=True, out=cat3.slice(0, fo[0]))
+        if pre is None:
+            self.conv_bn(v3, n + ".f3_v_proj.0", n + ".f3_v_proj.1", fo[0], k=3, pad=1, pool=True, out=cat3.slice(0, fo[0]))
+        else:
+            self._gather(pre["p3"], index, B, out=cat3.slice(0, fo[0]))
         f3 = self.conv_bn(cat3, n + ".f3_cat.0", n + ".f3_cat.1", fo[1])
         # fusion 4
-        cat4 = self.new_act(v4.Bn, v4.H, v4.W, 3 * fo[1])
+        cat4 = self.new_act(B, H4, W4, 3 * fo[1])
         # the three 3x3 convolutions of fusion 4 (model/layers.py:300-302) read f5 / f4 / f3 and write three buffers; their input
         # gradients go to three buffers as well: one grouped launch each way, see _group_variant
         G = self.group_begin()
@@ -854,7 +867,7 @@ class Engine:
         self.bn(y3p, s3p, n + ".f4_proj3.1", out=cat4.slice(0, fo[1]))
         self._upsample(fq5, cat4.slice(2 * fo[1], fo[1]))
         # aggregation + CoordConv (2 coordinate channels, zero padded to a multiple of 8)
-        cc = self.new_act(v4.Bn, v4.H, v4.W, pad8(fo[1] + 2))
+        cc = self.new_act(B, H4, W4, pad8(fo[1] + 2))
         self.conv_bn(cat4, n + ".aggr.0", n + ".aggr.1", fo[1], out=cc.slice(0, fo[1]))
         ops.fill_coords(cc.t, cc.ld, fo[1], cc.ld - fo[1], cc.Bn, cc.H, cc.W)
         self._neck_taps = dict(f5=f5, f4=f4, f3=f3, aggr=cc.slice(0, fo[1]), s=s if s is not None else s32)
@@ -900,6 +913,14 @@ class Engine:
             ops.linear_f32_small(dys, W, gst, w_is_kn=True, accumulate=acc)   # dstate[b][e] (+)= sum_c dys[b][c] W[c][e]
 
         return s32, bwd
+
+    def _gather(self, x: Act, index, K: int, out: Optional[Act] = None) -> Act:
+        """out[k] = x[index[k]] per sample (inference only: no tape entry)"""
+        assert not self.training
+        if out is None:
+            out = self.new_act(K, x.H, x.W, x.C)
+        ops.gather_samples(x.t, index, K, x.H * x.W, x.C, out.t, ldx=x.ld, xcoff=x.coff, ldy=out.ld, ycoff=out.coff)
+        return out
 
     def _upsample(self, x: Act, out: Act):
         ops.upsample2_fwd(x.t, x.Bn, x.H, x.W, x.C, out.t, ldx=x.ld, xcoff=x.coff, ldy=out.ld, ycoff=out.coff)
@@ -1037,7 +1058,8 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     # whole step
     # ------------------------------------------------------------------------------------------
-    def forward(self, img, word, mask=None, training=True, seed=0, taps: Optional[dict] = None):
+    def _begin_forward(self, word, training, seed):
+        """state of a new forward (tape, queues, zero slab, weight packs); returns the validated int64 token ids"""
         self.training, self.seed = training, int(seed) & 0xFFFFFFFF
         self.tape = []
         self._wq, self._sq = ops.WgradQueue(self._flush_wgrads), ops.SumQueue()      # (drops what a forward without backward left queued)
@@ -1059,6 +1081,10 @@ class Engine:
         if word.shape[1] > self.P["backbone.positional_embedding"].shape[0]:
             raise ValueError("expression length %d exceeds the text context length %d"
                              % (word.shape[1], self.P["backbone.positional_embedding"].shape[0]))
+        return word
+
+    def forward(self, img, word, mask=None, training=True, seed=0, taps: Optional[dict] = None):
+        word = self._begin_forward(word, training, seed)
         main = torch.cuda.current_stream()
         self._text_tape_start = 0
         self._vis_stage_start = {}

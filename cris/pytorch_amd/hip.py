@@ -274,6 +274,7 @@ _SIGS = {
     "cris_upsample2_fwd": (I, [P, I, I, I, I, I, I, P, I, I, P]),
     "cris_upsample2_bwd": (I, [P, I, I, I, I, I, I, P, I, I, I, P]),
     "cris_fill_coords": (I, [P, I, I, I, I, I, I, P]),
+    "cris_gather_samples_bf16": (I, [P, I, I, P, I, I, I, P, I, I, P]),
     "cris_add_bf16": (I, [P, I, I, P, I, I, P, I, I, I, I, P]),
     "cris_add_rowtable": (I, [P, I, P, I, P, I, I, I, P]),
     "cris_cast_f32_bf16": (I, [P, P, L, P]),

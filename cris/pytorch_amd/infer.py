@@ -17,6 +17,7 @@ post-processing: sigmoid + bicubic upsampling to the input size, evalpost.py) ca
 """
 from __future__ import annotations
 
+import numbers
 from typing import Dict, Optional
 
 import torch
@@ -52,6 +53,48 @@ class InferEngine(Engine):
             self.packs_current = True       # frozen weights: the bf16 operand copies made by this forward stay valid
             self._zneed_last = max(self._zneed_last, self._zneed)      # size of the zero slab the next forward carves from
         return out
+
+    def forward_multi(self, img, word, index):
+        """Several expressions per image: img [B, 3, S, S], word [K, L], index device int32 [K] (the image of each expression,
+        every entry in [0, B) - the caller checks) -> logits [K, 1, S/4, S/4].  The image stage - the visual encoder and the
+        three image-side neck convolutions (neck.f1_v_proj before its BatchNorm, f2_v_proj, f3_v_proj + pool), none of which
+        reads the sentence - runs ONCE per image at batch B; the expression stage - the text encoder (side stream, as in
+        forward), the rest of the neck from the per-sample gathers of those three maps on, the decoder and the projector -
+        runs at batch K.  forward() is this with B == K and index = arange(K), minus the three gathers."""
+        word = self._begin_forward(word, False, 0)
+        main = torch.cuda.current_stream()
+        self._vis_stage_start = {}
+        if self.side is not None:
+            ops.torch_op(lambda: self.side.wait_stream(main))
+            with torch.cuda.stream(self.side):
+                txt, state = self._encode_text(word)
+        else:
+            txt, state = self._encode_text(word)
+        v3, v4, v5, _ = self._encode_image(img.contiguous().float())
+        pre = self._fpn_image(v3, v4, v5)
+        if self.side is not None:
+            ops.torch_op(lambda: main.wait_stream(self.side))
+        fq = self._fpn(None, None, None, state, pre=pre, index=index)
+        fqd = self._decoder(fq, Act(txt.t, txt.Bn, txt.H, 1, txt.C, root=txt.root), word)
+        pred, _, _ = self._projector(fqd, state)
+        Act._engine = None
+        self.packs_current = True
+        self._zneed_last = max(self._zneed_last, self._zneed)
+        return pred
+
+    def _fpn_image(self, v3: Act, v4: Act, v5: Act) -> dict:
+        """the sentence-independent layers of the neck at the image batch (Engine._fpn reads their outputs through `pre`):
+        y5 = f1_v_proj's convolution (its BatchNorm is applied after the gather, with the per-sample multiplication), p2 / p3 =
+        relu(bn(f2_v_proj(v4))) / avgpool(relu(bn(f3_v_proj(v3)))) in buffers of their own - the same launches as in _fpn"""
+        n = "neck"
+        fo = self.head.fpn_out
+        y5, _ = self.gemm(v5, n + ".f1_v_proj.0.weight", fo[2], stats=True)
+        pd = y5.aux.pop("pending", None)
+        if pd is not None:                                  # folded mode: the launch bn(mul=...) would issue, unfolded
+            y5 = self._launch(pd, self.WF[pd.wname], None, 0, None, None)
+        p2 = self.conv_bn(v4, n + ".f2_v_proj.0", n + ".f2_v_proj.1", fo[1], k=3, pad=1)
+        p3 = self.conv_bn(v3, n + ".f3_v_proj.0", n + ".f3_v_proj.1", fo[0], k=3, pad=1, pool=True)
+        return dict(y5=y5, p2=p2, p3=p3)
 
     def invalidate(self):
         """parameters or running statistics changed (load_state_dict): fold and pack again on the next forward"""
@@ -163,35 +206,90 @@ class InferenceRunner:
 
     def _body(self, img, word):
         pred = self.engine.forward(img, word, None, training=False)
+        return self._post(pred, img)
+
+    def _body_multi(self, img, word, index):
+        return self._post(self.engine.forward_multi(img, word, index), img)
+
+    def _post(self, pred, img):
         if not self.upsample:
             return pred
         from . import evalpost
         return evalpost.sigmoid_upsample(pred, img.shape[-2], img.shape[-1])
 
-    @torch.no_grad()
-    def __call__(self, img, word):
-        if not self.use_graph:
-            return self._body(img, word)
-        key = (tuple(img.shape), tuple(word.shape))
+    def _run(self, key, body, inputs):
+        """body(*static copies of inputs) for one shape key: eager on the first call, captured on the second, replayed after"""
         st = self._shapes.get(key)
         if st is None:
-            st = self._shapes[key] = dict(calls=0, img=img.clone(), word=word.clone(), graph=None, out=None)
+            # (a host input - segment's image index - gets a device buffer of its own)
+            st = self._shapes[key] = dict(calls=0, graph=None, out=None,
+                                          inputs=[t.clone() if t.device.type != "cpu" else torch.empty(t.shape, dtype=t.dtype, device=self.device)
+                                                  for t in inputs])
         st["calls"] += 1
-        st["img"].copy_(img, non_blocking=True)
-        st["word"].copy_(word, non_blocking=True)
+        for dst, src in zip(st["inputs"], inputs):
+            dst.copy_(src, non_blocking=True)
         if st["calls"] == 1:
-            return self._body(st["img"], st["word"])
+            return body(*st["inputs"])
         if st["graph"] is None and self.graph_error is None:
             try:
                 from . import capture
                 g = torch.cuda.CUDAGraph()
                 with capture.graph(g, device=self.device):
-                    out = self._body(st["img"], st["word"])
+                    out = body(*st["inputs"])
                 st["graph"], st["out"] = g, out
             except Exception as ex:          # noqa: BLE001
                 self.graph_error = repr(ex)
                 torch.cuda.synchronize(self.device)
         if st["graph"] is None:
-            return self._body(st["img"], st["word"])
+            return body(*st["inputs"])
         st["graph"].replay()
         return st["out"]
+
+    @torch.no_grad()
+    def __call__(self, img, word):
+        if not self.use_graph:
+            return self._body(img, word)
+        return self._run((tuple(img.shape), tuple(word.shape)), self._body, (img, word))
+
+    @torch.no_grad()
+    def segment(self, img, word, image_index):
+        """Several referring expressions per image with one visual pass: img [B, 3, S, S], word [K, L], image_index (a host
+        sequence or CPU integer tensor of K values in [0, B): the image of each expression) -> logits [K, 1, S/4, S/4], or
+        with `upsample=True` probabilities [K, S, S]; row k is what `runner(img[image_index], word)` computes for expression k.
+        The visual encoder and the image-side neck convolutions run at batch B (InferEngine.forward_multi).  Like __call__:
+        one HIP graph per (B, S, K, L) - a new index content replays it - and the returned buffer is overwritten by the next
+        call."""
+        idx = self._check_index(img, word, image_index)
+        if torch.device(self.device).type == "cuda":
+            idx = idx.pin_memory()           # the copy to the static index buffer is asynchronous
+        if not self.use_graph:
+            return self._body_multi(img, word, idx.to(self.device, non_blocking=True))
+        return self._run(("segment", tuple(img.shape), tuple(word.shape)), self._body_multi, (img, word, idx))
+
+    @staticmethod
+    def _check_index(img, word, image_index) -> torch.Tensor:
+        """image_index -> CPU int32 [K], or ValueError"""
+        if img.dim() != 4 or word.dim() != 2:
+            raise ValueError("segment: img must be [B, 3, S, S] and word [K, L], got %s and %s" % (tuple(img.shape), tuple(word.shape)))
+        if isinstance(image_index, torch.Tensor):
+            if image_index.device.type != "cpu":
+                raise ValueError("segment: image_index must be a host sequence or a CPU tensor, got a tensor on %s (checking it "
+                                 "would synchronise with the device)" % image_index.device)
+            if image_index.dim() != 1 or image_index.is_floating_point() or image_index.is_complex() or image_index.dtype == torch.bool:
+                raise ValueError("segment: image_index must be a 1-d integer tensor, got %s %s"
+                                 % (image_index.dtype, tuple(image_index.shape)))
+            idx = image_index.to(torch.int64)
+        else:
+            vals = list(image_index)
+            if not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in vals):
+                raise ValueError("segment: image_index must hold integers")
+            idx = torch.tensor(vals, dtype=torch.int64).reshape(-1)
+        K, B = idx.numel(), img.shape[0]
+        if K == 0:
+            raise ValueError("segment: no expressions (K = 0)")
+        if K != word.shape[0]:
+            raise ValueError("segment: %d image indices for %d expressions (word has %d rows)" % (K, word.shape[0], word.shape[0]))
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= B:
+            raise ValueError("segment: image index %d out of range [0, %d)" % (lo if lo < 0 else hi, B))
+        return idx.to(torch.int32)

@@ -617,6 +617,23 @@ class CRIS(nn.Module):
         folded into their convolutions, one HIP graph per input shape (infer.py).  The folded weights are a cache of the
         parameters and running statistics: it is rebuilt when any of them changed since it was made - torch's version counters
         see optimizer steps and load_state_dict, `_steps` sees the running statistics the HIP training forward updates."""
+        return self._infer_runner(img)(img.float().contiguous(), word).clone()          # (the runner's buffer is overwritten by its next call)
+
+    def segment_expressions(self, img, word, image_index):
+        """Several referring expressions per image with one visual pass (eval mode only): img [B, 3, h, w], word [K, words],
+        image_index: a host sequence or CPU integer tensor of K values in [0, B), the image of each expression.  Returns the
+        logits [K, 1, h/4, w/4] that `model(img[image_index], word)` computes, running the visual encoder once per IMAGE
+        (infer.InferenceRunner.segment; the same folded-weight cache as the eval forward).  A new tensor."""
+        if self.training:
+            raise RuntimeError("segment_expressions is an inference call: put the model in eval() mode first")
+        if img.device.type != "cuda":
+            raise RuntimeError("CRIS (HIP path) runs on the GPU only: got an input on %s - there is no CPU fallback" % img.device)
+        self._ensure_engine(img.device)
+        with torch.no_grad():
+            return self._infer_runner(img).segment(img.float().contiguous(), word, image_index).clone()
+
+    def _infer_runner(self, img):
+        """the inference runner on the engine's tensors, refolded when the parameters / running statistics changed"""
         from ..infer import InferenceRunner
         eng = self._engine
         if getattr(self, "_ver_key", None) != self._engine_key:          # (the tensor objects change with .cuda() / .to())
@@ -629,4 +646,4 @@ class CRIS(nn.Module):
         elif sig != self._infer_sig:
             self._infer.invalidate()
             self._infer_sig = sig
-        return self._infer(img.float().contiguous(), word).clone()           # (the runner's buffer is overwritten by its next call)
+        return self._infer

@@ -728,6 +728,14 @@ def upsample2_bwd(dy, Bn, H, W, C_, dx, lddy=None, dycoff=0, lddx=None, dxcoff=0
              lddx if lddx is not None else dx.shape[-1], dxcoff, int(accum), _stream())
 
 
+def gather_samples(x, index, K, rows_per_sample, C_, y, ldx=None, xcoff=0, ldy=None, ycoff=0):
+    """y[k*R + r][ycoff:ycoff+C] = x[index[k]*R + r][xcoff:xcoff+C] (bf16 rows; index: device int32 [K] whose entries the
+    caller has checked against the samples of x)"""
+    assert index.dtype == torch.int32 and index.numel() >= K
+    hip.call("cris_gather_samples_bf16", ptr(x), ldx if ldx is not None else x.shape[-1], xcoff, ptr(index), K, rows_per_sample, C_,
+             ptr(y), ldy if ldy is not None else y.shape[-1], ycoff, _stream())
+
+
 def fill_coords(x, ldx, coff, nfill, Bn, H, W):
     hip.call("cris_fill_coords", ptr(x), ldx, coff, nfill, Bn, H, W, _stream())
 

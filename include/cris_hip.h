@@ -356,6 +356,11 @@ int cris_upsample2_fwd(const cris_bf16* x, int ldx, int xcoff, int Bn, int H, in
                        int ycoff, void* stream);
 int cris_upsample2_bwd(const cris_bf16* dy, int lddy, int dycoff, int Bn, int H, int W, int C, cris_bf16* dx,
                        int lddx, int dxcoff, int accum, void* stream);
+/* sample gather (several expressions of one image: infer.InferEngine.forward_multi):
+ * y[k*R + r][ycoff + c] = x[index[k]*R + r][xcoff + c] for k < K, r < R = rows_per_sample, c < C.  index: device int32 [K],
+ * every entry in [0, samples of x) - validated by the caller, not by the kernel.  Exact copies. */
+int cris_gather_samples_bf16(const cris_bf16* x, int ldx, int xcoff, const int32_t* index, int K, int rows_per_sample, int C,
+                             cris_bf16* y, int ldy, int ycoff, void* stream);
 /* CoordConv coordinate channels (model/layers.py:30-39): x at column coff, y at coff+1, zeros up to coff+nfill */
 int cris_fill_coords(cris_bf16* x, int ldx, int coff, int nfill, int Bn, int H, int W, void* stream);
 /* generic strided bf16 ops: y (=|+=) a [+ b] ;  and y = a + f32 table[row % trows] */
