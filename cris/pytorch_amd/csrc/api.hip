@@ -23,6 +23,8 @@ extern "C" int cris_sizeof(const char* name) {
     S(cris_conv_gemm_group);
     S(cris_wgrad_group);
     S(cris_pack_desc);
+    S(cris_conv_gemm_fp8_params);
+    S(cris_pack_fp8_desc);
     S(cris_bn_apply_params);
     S(cris_bn_bwd_params);
     S(cris_ln_fwd_params);

@@ -70,6 +70,25 @@ class PackDesc(C.Structure):
                 ("block_start", I), ("ldF", I), ("ldD", I), ("pad_", I)]
 
 
+class ConvGemmFp8Params(C.Structure):
+    _fields_ = [("A", P), ("Wt", P), ("e_w", P), ("bias", P), ("resid", P), ("out", P), ("out8", P),
+                ("lda", I), ("a_coff", I),
+                ("Bn", I), ("H", I), ("W", I), ("C", I),
+                ("OH", I), ("OW", I), ("KH", I), ("KW", I), ("stride", I), ("pad", I),
+                ("ldb", I),
+                ("M", I), ("N", I), ("K", I),
+                ("act", I),
+                ("ldr", I), ("r_coff", I),
+                ("ldc", I), ("c_coff", I),
+                ("ldq", I), ("q_coff", I),
+                ("e_x", I), ("e_y", I)]
+
+
+class PackFp8Desc(C.Structure):
+    _fields_ = [("src", P), ("row_scale", P), ("dst", P), ("e_w", P),
+                ("N", I), ("Cin", I), ("taps", I), ("Cpad", I), ("ld", I), ("block_start", I)]
+
+
 class BnApplyParams(C.Structure):
     _fields_ = [("y", P), ("ldy", I), ("y_coff", I),
                 ("scale", P), ("shift", P),
@@ -222,6 +241,7 @@ class P2PArenaParams(C.Structure):
 
 STRUCTS = {
     "cris_conv_gemm_params": ConvGemmParams, "cris_conv_gemm_group": ConvGemmGroup, "cris_wgrad_params": WgradParams, "cris_wgrad_group": WgradGroup, "cris_pack_desc": PackDesc,
+    "cris_conv_gemm_fp8_params": ConvGemmFp8Params, "cris_pack_fp8_desc": PackFp8Desc,
     "cris_bn_apply_params": BnApplyParams, "cris_bn_bwd_params": BnBwdParams, "cris_ln_fwd_params": LnFwdParams,
     "cris_ln_bwd_params": LnBwdParams, "cris_sum_entry": SumEntry, "cris_sum_group": SumGroup, "cris_attn_params": AttnParams, "cris_adam_desc": AdamDesc, "cris_p2p_params": P2PParams, "cris_p2p_link": P2PLink, "cris_p2p_arena_params": P2PArenaParams, "cris_zero_ranges": ZeroRanges,
     "cris_sample_desc": SampleDesc, "cris_jpeg_info": JpegInfo, "cris_jpeg_image": JpegImage,
@@ -251,6 +271,14 @@ _SIGS = {
     "cris_conv_gemm_plan": (I, [P, I, P]),
     "cris_conv_gemm_group_launch": (I, [P, I, P]),
     "cris_conv_gemm_variant_name": (C.c_char_p, [I]),
+    "cris_conv_gemm_fp8": (I, [P, I, P]),
+    "cris_conv_gemm_fp8_plan": (I, [P, I]),
+    "cris_conv_gemm_fp8_num_variants": (I, []),
+    "cris_conv_gemm_fp8_variant_name": (C.c_char_p, [I]),
+    "cris_pack_weights_fp8": (I, [P, I, I, P]),
+    "cris_avgpool2_fwd_fp8": (I, [P, I, I, I, I, I, I, P, I, I, P, I, I, I, P]),
+    "cris_absmax_bf16": (I, [P, I, I, L, I, P, P, P]),
+    "cris_absmax_ws_floats": (I, []),
     "cris_bn_partials_rows": (I, [I]),
     "cris_bn_finalize": (I, [P, P, I, I, F, F, P, P, P, P, F, F, I, P, P, P, P, P, P, P]),
     "cris_bn_sync_pack": (I, [P, P, P, F, I, P]),
@@ -360,7 +388,7 @@ class HipLibraryError(RuntimeError):
     pass
 
 
-ABI_VERSION = 4      # == CRIS_ABI_VERSION of include/cris_hip.h (tests/test_abi.py compares the two)
+ABI_VERSION = 5      # == CRIS_ABI_VERSION of include/cris_hip.h (tests/test_abi.py compares the two)
 
 
 def load():

@@ -6,6 +6,7 @@ current HIP stream.  Every function launches on `torch.cuda.current_stream()`.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -1050,3 +1051,116 @@ class UnpackTable:
 
     def run(self):
         hip.call("cris_unpack_grads", ptr(self.dev), self.n, self.total_blocks, _stream())
+
+
+# ---- FP8 inference (csrc/gemm_fp8.hip) ---------------------------------------------------------
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+
+
+def fp8_exponent(amax: float, headroom: float = 1.0) -> int:
+    """the smallest integer e with amax * 2^-e <= 448 / headroom (0 when amax is 0): the power-of-two scale of a tensor whose
+    largest magnitude is amax.  headroom 1 is the weight rule (the packing kernel computes the same on the device)."""
+    amax = float(amax)
+    if not amax > 0.0:
+        return 0
+    if amax != amax or amax == float("inf"):
+        raise ValueError("fp8 scale of a non-finite abs-max")
+    lim = FP8_MAX / float(headroom)
+    m, q = math.frexp(amax / lim)            # (a first guess; the exact test below decides)
+    e = q if m > 0.5 else q - 1
+    while math.ldexp(amax, -e) > lim:
+        e += 1
+    while math.ldexp(amax, -(e - 1)) <= lim:
+        e -= 1
+    return e
+
+
+def quantise_fp8_reference(x: torch.Tensor, e: int) -> torch.Tensor:
+    """what the kernels store for a float32 tensor x with exponent e (torch on any device; the definition, not a hot path)"""
+    return (x.float() * 2.0 ** -e).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+
+
+def gemm_fp8_variants():
+    """names of the fp8 conv tile variants, by index (cris_conv_gemm_fp8)"""
+    lib = hip.load()
+    return [lib.cris_conv_gemm_fp8_variant_name(i).decode() for i in range(lib.cris_conv_gemm_fp8_num_variants())]
+
+
+def conv_gemm_fp8(A8, W8, e_w, g: Geom, N: int, e_x: int, *, lda=None, a_coff=0, ldb=None, bias=None, act=0, resid=None, ldr=None,
+                  r_coff=0, out=None, ldc=None, c_coff=0, out8=None, ldq=None, q_coff=0, e_y=0, variant=-1):
+    """x = (A8_im2col @ W8^T) * 2^(e_x + e_w[n]) + bias, act (1: relu; 3: relu after the residual), + resid (bf16);
+    out (bf16) and / or out8 (fp8, exponent e_y).  A8 fp8 NHWC (row stride lda, C % 16 == 0), W8 fp8 [N][ldb], e_w int32 [N]."""
+    p = hip.ConvGemmFp8Params()
+    p.A, p.Wt, p.e_w, p.bias = ptr(A8), ptr(W8), ptr(e_w), ptr(bias)
+    p.lda = lda if lda is not None else A8.shape[-1]
+    p.a_coff = a_coff
+    p.Bn, p.H, p.W, p.C = g.Bn, g.H, g.W, g.C
+    p.OH, p.OW, p.KH, p.KW, p.stride, p.pad = g.OH, g.OW, g.KH, g.KW, g.stride, g.pad
+    p.ldb = ldb if ldb is not None else W8.shape[-1]
+    p.M, p.N, p.K = g.M, N, g.K
+    p.act = act
+    if resid is not None:
+        p.resid, p.ldr, p.r_coff = ptr(resid), ldr if ldr is not None else resid.shape[-1], r_coff
+    if out is not None:
+        p.out, p.ldc, p.c_coff = ptr(out), ldc if ldc is not None else out.shape[-1], c_coff
+    if out8 is not None:
+        p.out8, p.ldq, p.q_coff = ptr(out8), ldq if ldq is not None else out8.shape[-1], q_coff
+    p.e_x, p.e_y = int(e_x), int(e_y)
+    if isinstance(variant, str):
+        variant = gemm_fp8_variants().index(variant)
+    flops, nbytes = 2.0 * g.M * N * g.K, float(g.M * g.C + N * g.K + 2 * g.M * N)
+    if KERNEL_TIMER is not None:
+        KERNEL_TIMER.launch("conv_gemm_fp8", flops, nbytes, "cris_conv_gemm_fp8", C.byref(p), variant,
+                            tag="M%d N%d K%d k%d" % (g.M, N, g.K, g.KH), tile=True)
+        return
+    hip.call("cris_conv_gemm_fp8", C.byref(p), variant, _stream())
+
+
+class PackTableFp8:
+    """Device-resident table of cris_pack_fp8_desc: one launch quantises and packs every weight of the table (folded by its
+    row_scale) into the fp8 GEMM layout [N][taps * Cpad] (Cpad = Cin rounded up to 16) with its per-row exponents."""
+
+    def __init__(self):
+        self.descs, self.keep, self.dev, self.total_blocks = [], [], None, 0
+
+    def add(self, src, N, Cin, taps, row_scale=None):
+        Cpad = (Cin + 15) // 16 * 16
+        ld = taps * Cpad
+        dst = torch.empty(N, ld, dtype=FP8, device=src.device)
+        e_w = torch.empty(N, dtype=torch.int32, device=src.device)
+        d = hip.PackFp8Desc()
+        d.src, d.row_scale, d.dst, d.e_w = ptr(src), ptr(row_scale), ptr(dst), ptr(e_w)
+        d.N, d.Cin, d.taps, d.Cpad, d.ld = N, Cin, taps, Cpad, ld
+        self.descs.append(d)
+        self.keep.append((src, row_scale, dst, e_w))
+        self.dev = None
+        return dst, e_w
+
+    def run(self):
+        if not self.descs:
+            return
+        if self.dev is None:
+            n = len(self.descs)
+            arr = (hip.PackFp8Desc * n)()
+            start = 0
+            for i, d in enumerate(self.descs):
+                d.block_start = start
+                start += d.N
+                arr[i] = d
+            self.total_blocks = start
+            self.dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.keep[0][0].device)
+        hip.call("cris_pack_weights_fp8", ptr(self.dev), len(self.descs), self.total_blocks, _stream())
+
+
+def avgpool2_fwd_fp8(x, Bn, H, W, C_, y8, e_y, ldx=None, xcoff=0, ldq=None, qcoff=0, y=None, ldy=None, ycoff=0):
+    """2x2 average pool (the arithmetic of avgpool2_fwd) -> fp8 y8 with exponent e_y (and the bf16 map y when given)"""
+    hip.call("cris_avgpool2_fwd_fp8", ptr(x), ldx if ldx is not None else x.shape[-1], xcoff, Bn, H, W, C_, ptr(y),
+             (ldy if ldy is not None else y.shape[-1]) if y is not None else 0, ycoff, ptr(y8), ldq if ldq is not None else y8.shape[-1],
+             qcoff, int(e_y), _stream())
+
+
+def absmax_bf16(x, rows, C_, out, ldx=None, xcoff=0):
+    """out[0] = max |x| over rows x C_ channels of a bf16 [rows][ldx] tensor (device, no host sync)"""
+    ws = torch.empty(hip.load().cris_absmax_ws_floats(), dtype=torch.float32, device=x.device)
+    hip.call("cris_absmax_bf16", ptr(x), ldx if ldx is not None else x.shape[-1], xcoff, rows, C_, ptr(ws), ptr(out), _stream())

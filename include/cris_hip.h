@@ -26,8 +26,8 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs) */
-#define CRIS_ABI_VERSION 4
+ * mis-read them silently).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels */
+#define CRIS_ABI_VERSION 5
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
 int cris_sizeof(const char* struct_name);
@@ -183,6 +183,62 @@ int cris_pack_weights(const cris_pack_desc* dev_table, int n_desc, int total_blo
 /* number of blocks a (host-side) descriptor needs: used to build block_start prefix sums on the host */
 int cris_pack_blocks(const cris_pack_desc* host_desc);
 int cris_pack_block_elems(void);
+
+/* ------------------------------------------------------------------------------------------------
+ * FP8 inference (csrc/gemm_fp8.hip; opt-in, no training path uses it).  OCP e4m3fn bytes, power-of-two scales:
+ *   quantise(x, e) = RNE_e4m3(clamp(x * 2^-e, -448, 448))  (bit for bit torch's (x * 2**-e).clamp(-448, 448).to(float8_e4m3fn))
+ * Implicit-GEMM convolution on the block-scaled MFMA (v_mfma_scale_f32_32x32x64_f8f6f4, unit block scales), fp32 accumulate:
+ *   x = sum_k A8[m, k] * W8[n, k] * 2^(e_x + e_w[n]) + bias[n];  act 1: relu;  x += resid[m, n] (bf16);  act 3: relu
+ *   out[m, n] = bf16(x) and / or out8[m, n] = quantise(x, e_y)
+ * m = (b, oh, ow) over an NHWC fp8 input [Bn, H, W, lda] (channels a_coff .. a_coff+C), k = tap*C + c; C % 16 == 0.
+ * Tile variants 128x128 and 64x64 (cris_conv_gemm_fp8_plan; `variant` < 0 = chosen from the problem size).  No atomics;
+ * the results are deterministic and the same for every variant. */
+typedef struct {
+    const uint8_t* A;        /* NHWC fp8 input, row stride lda bytes */
+    const uint8_t* Wt;       /* [N][ldb] fp8 weights (cris_pack_weights_fp8), k contiguous */
+    const int* e_w;          /* [N] weight exponents */
+    const float* bias;       /* [N] or NULL */
+    const cris_bf16* resid;  /* [M][ldr] (+r_coff) bf16 or NULL */
+    cris_bf16* out;          /* [M][ldc] (+c_coff) bf16 or NULL */
+    uint8_t* out8;           /* [M][ldq] (+q_coff) fp8 or NULL */
+    int lda, a_coff;
+    int Bn, H, W, C;
+    int OH, OW, KH, KW, stride, pad;
+    int ldb;
+    int M, N, K;
+    int act;                 /* 0 none, 1 relu before the residual, 3 relu after it (cris_conv_gemm_params.act) */
+    int ldr, r_coff;
+    int ldc, c_coff;
+    int ldq, q_coff;
+    int e_x;                 /* activation exponent: the real input is A8 * 2^e_x */
+    int e_y;                 /* exponent of the fp8 output */
+} cris_conv_gemm_fp8_params;
+int cris_conv_gemm_fp8(const cris_conv_gemm_fp8_params* p, int variant, void* stream);
+/* the tile variant cris_conv_gemm_fp8(p, variant) runs (-1: out of range); host only */
+int cris_conv_gemm_fp8_plan(const cris_conv_gemm_fp8_params* p, int variant);
+int cris_conv_gemm_fp8_num_variants(void);
+const char* cris_conv_gemm_fp8_variant_name(int variant);
+/* Weight quantise + pack, one launch for a table of tensors, one block per output channel (block_start: prefix sums of N):
+ *   v = src[n][c][tap] * row_scale[n] (the folded fp32 weight of cris_pack_desc), e_w[n] = the smallest integer with
+ *   max |v| * 2^-e_w[n] <= 448 (0 for an all-zero row), dst[n][tap*Cpad + c] = quantise(v, e_w[n]); channels Cin .. Cpad-1 and
+ *   columns taps*Cpad .. ld-1 are written as zeros. */
+typedef struct {
+    const float* src;        /* [N][Cin][taps] */
+    const float* row_scale;  /* [N] or NULL */
+    uint8_t* dst;            /* [N][ld] */
+    int* e_w;                /* [N] */
+    int N, Cin, taps, Cpad, ld;
+    int block_start;
+} cris_pack_fp8_desc;
+int cris_pack_weights_fp8(const cris_pack_fp8_desc* dev_table, int n_desc, int total_blocks, void* stream);
+/* 2x2 / stride 2 average pool of an NHWC bf16 map (the arithmetic of cris_avgpool2_fwd) with an fp8 output quantise(y, e_y)
+ * [Bn*H/2*W/2][ldq] (+qcoff); y (bf16, the same values unrounded by fp8) is optional (NULL) */
+int cris_avgpool2_fwd_fp8(const cris_bf16* x, int ldx, int xcoff, int Bn, int H, int W, int C, cris_bf16* y, int ldy, int ycoff,
+                          uint8_t* y8, int ldq, int qcoff, int e_y, void* stream);
+/* max |x| over an NHWC bf16 tensor [rows][ldx] (channels xcoff .. xcoff+C) -> out[0] (calibration of the activation scales);
+ * ws: cris_absmax_ws_floats() floats.  Two launches, no atomics. */
+int cris_absmax_bf16(const cris_bf16* x, int ldx, int xcoff, long rows, int C, float* ws, float* out, void* stream);
+int cris_absmax_ws_floats(void);
 
 
 /* ------------------------------------------------------------------------------------------------
