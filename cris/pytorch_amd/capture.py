@@ -13,13 +13,16 @@ watchdog had retired them).  Two independent measures, both applied by `graph()`
     (`drain_c10d`: device synchronisation + a few of its polling periods) - so that even a runtime that ignored the mode
     would find nothing left to query.
 
-Every capture of the package (trainer, drop-in module, inference runner) goes through here.
+`build()` is the one way a schedule of the package (trainer, drop-in module, inference runner) becomes replayable: a HIP
+graph captured through `graph()`, or a host command list recorded under `hip.recording` into a MemPool that the list keeps.
 """
 import contextlib
 import os
 import time
 
 import torch
+
+from . import hip
 
 # the watchdog sleeps kWatchdogThreadSleepMillis = 100 ms between passes over its work list
 _WATCHDOG_PERIODS_S = float(os.environ.get("CRIS_CAPTURE_DRAIN_S", "0.35"))
@@ -53,3 +56,34 @@ def graph(g, pool=None, device=None, drain=True):
     kw = {} if pool is None else {"pool": pool}
     with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE, **kw):
         yield g
+
+
+def shared_pool(mode):
+    """a memory pool for several programs of one `mode` that build() makes in turn (the drop-in module's forward and backward)"""
+    return torch.cuda.graph_pool_handle() if mode == "graph" else torch.cuda.MemPool()
+
+
+def build(mode, body, *, pool=None, device=None, drain=True):
+    """body() as a replayable program -> (program, body's result); `program.replay()` issues the schedule again.
+    "graph": a CUDAGraph captured through graph() - body has NOT run.  "cmdlist": a hip.CommandList - body HAS run once
+    while it was recorded, allocating from `pool` (a new MemPool by default), which the list keeps."""
+    if mode == "graph":
+        g = torch.cuda.CUDAGraph()
+        with graph(g, pool=pool, device=device, drain=drain):
+            out = body()
+        return g, out
+    assert mode == "cmdlist", mode
+    cmds = hip.CommandList(pool if pool is not None else torch.cuda.MemPool())
+    with torch.cuda.use_mem_pool(cmds.pool), hip.recording(cmds):
+        out = body()
+    return cmds, out
+
+
+def stage(static, inputs, device):
+    """the static input buffers a replayed schedule reads: clones of `inputs` when `static` is None (a host tensor gets a
+    device buffer of its own), else `static` with the new values copied in asynchronously"""
+    if static is None:
+        return [t.clone() if t.device.type != "cpu" else t.to(device, non_blocking=True) for t in inputs]
+    for dst, src in zip(static, inputs):
+        dst.copy_(src, non_blocking=True)
+    return static

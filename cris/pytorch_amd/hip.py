@@ -4,6 +4,7 @@
 the process).  The product path FAILS LOUDLY when the library is missing or was
 not built - there is no CPU / eager fallback anywhere in cris.pytorch_amd.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -428,10 +429,12 @@ class CommandList:
     """Host-side command list of one step: every libcris_hip launch (function + ctypes arguments, stream included) and
     every torch-level op (stream wait, collective) in issue order.  Replaying it costs a few microseconds of Python per
     entry instead of the schedule's Python (closures, struct filling, allocations) - the launch mode used where a HIP graph
-    is not (collectives inside the step).  All buffers the commands point to must stay allocated (trainer.py: MemPool)."""
+    is not (collectives inside the step).  `pool` is the MemPool the recorded step allocated its buffers from
+    (capture.build): the list holds it, so the memory its commands point into lives exactly as long as the list."""
 
-    def __init__(self):
+    def __init__(self, pool=None):
         self.cmds = []
+        self.pool = pool
 
     def replay(self):
         for fn, args, name in self.cmds:
@@ -443,7 +446,21 @@ class CommandList:
                     check(rc, name)
 
 
-RECORDER = None          # a CommandList while a step is being recorded
+RECORDER = None          # a CommandList while a step is being recorded (assigned by `recording` only)
+
+
+@contextlib.contextmanager
+def recording(cmdlist):
+    """`with hip.recording(cl)`: every launch (call) and torch-level op (ops.torch_op) issued inside the block is appended
+    to `cl` as it runs.  Recordings do not nest; RECORDER is None again on any exit."""
+    global RECORDER
+    if RECORDER is not None:
+        raise RuntimeError("hip.recording: a command list is already being recorded")
+    RECORDER = cmdlist
+    try:
+        yield cmdlist
+    finally:
+        RECORDER = None
 
 
 def call(name, *args):

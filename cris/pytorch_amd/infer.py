@@ -22,7 +22,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import ops
+from . import capture, ops
 from .arch import ClipSpec, HeadSpec
 from .engine import Act, BN_EPS, Engine
 from .ops import Geom, pad8
@@ -219,24 +219,14 @@ class InferenceRunner:
 
     def _run(self, key, body, inputs):
         """body(*static copies of inputs) for one shape key: eager on the first call, captured on the second, replayed after"""
-        st = self._shapes.get(key)
-        if st is None:
-            # (a host input - segment's image index - gets a device buffer of its own)
-            st = self._shapes[key] = dict(calls=0, graph=None, out=None,
-                                          inputs=[t.clone() if t.device.type != "cpu" else torch.empty(t.shape, dtype=t.dtype, device=self.device)
-                                                  for t in inputs])
+        st = self._shapes.setdefault(key, dict(calls=0, inputs=None, graph=None, out=None))
         st["calls"] += 1
-        for dst, src in zip(st["inputs"], inputs):
-            dst.copy_(src, non_blocking=True)
+        st["inputs"] = capture.stage(st["inputs"], inputs, self.device)
         if st["calls"] == 1:
             return body(*st["inputs"])
         if st["graph"] is None and self.graph_error is None:
             try:
-                from . import capture
-                g = torch.cuda.CUDAGraph()
-                with capture.graph(g, device=self.device):
-                    out = body(*st["inputs"])
-                st["graph"], st["out"] = g, out
+                st["graph"], st["out"] = capture.build("graph", lambda: body(*st["inputs"]), device=self.device)
             except Exception as ex:          # noqa: BLE001
                 self.graph_error = repr(ex)
                 torch.cuda.synchronize(self.device)

@@ -20,10 +20,15 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
-from .. import arch, debug, ops
+from .. import arch, capture, debug, ops
 from ..engine import Engine
 
 _FP16_ROUNDED_SUFFIXES = ("in_proj_weight", "in_proj_bias", "q_proj_weight", "k_proj_weight", "v_proj_weight")
+
+
+def _seed_word(seed):
+    """the uint32 dropout seed's bit pattern in the int32 device word"""
+    return ((int(seed) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000
 
 
 def _cfg_get(cfg, key, default=None):
@@ -108,14 +113,13 @@ class _CrisStep(torch.autograd.Function):
         if xchg is not None:
             module._exchange_stale_grads(xchg)   # gradients of no_sync() micro-batches still sitting in `.grad`
         st = ctx.graph
-        if st is not None and st.get("bwd") is None:
-            # command-list mode, first step with this shape: the forward was recorded while it ran, now the backward is
+        if st is not None:
             st["gscale"].copy_(gscale, non_blocking=True)
-            module._record_backward(st, xchg)
-            grads = st["grads"]
-        elif st is not None:
-            st["gscale"].copy_(gscale, non_blocking=True)
-            st["bwd"].replay()
+            if st["bwd"] is None:
+                # command-list mode, first step with this shape: the forward was recorded while it ran, now the backward is
+                module._build_programs(st, "cmdlist", st["fwd"].pool, xchg, ("bwd",))
+            else:
+                st["bwd"].replay()
             grads = st["grads"]
         else:
             module._backward_and_exchange(gscale, xchg)
@@ -430,10 +434,11 @@ class CRIS(nn.Module):
     # ------------------------------------------------------------------------------------------------
     # HIP-graph replay of the training step under torch's autograd.  The engine's schedule is ~1000 launches; issued from
     # Python one by one it is host-bound (37.5 ms per R50 step against 13.8 for the native trainer, bench.py --path module,
-    # round 3).  So the module captures, per input shape, TWO graphs over one memory pool - forward + loss (incl. the re-pack
-    # of the bf16 operand copies: a torch optimizer changed the parameters) and backward + gradient export - and replays them
-    # from _CrisStep.forward / .backward.  Step-varying scalars live in device memory: the dropout seed (Engine.seed_dev) and
-    # GradScaler's factor (gscale).  First call of a shape runs eagerly (tables, allocator warm-up), the second captures.
+    # round 3).  So the module builds, per input shape, TWO programs over one memory pool (_build_programs) - forward + loss
+    # (incl. the re-pack of the bf16 operand copies: a torch optimizer changed the parameters) and backward + gradient export -
+    # and replays them from _CrisStep.forward / .backward.  Step-varying scalars live in device memory: the dropout seed
+    # (Engine.seed_dev) and GradScaler's factor (gscale).  First call of a shape runs eagerly (tables, allocator warm-up), the
+    # second captures.
     # Eager launches remain for: CRIS_MODULE_GRAPH=0, more than MAX_GRAPH_SHAPES shapes, a communicator whose collectives
     # cannot be captured (gloo), and any capture failure (reported once in `graph_error`).
     MAX_GRAPH_SHAPES = 6
@@ -456,17 +461,21 @@ class CRIS(nn.Module):
             if key not in self._graph_seen:
                 self._graph_seen.add(key)
                 return None                                                  # first step with these shapes: eager
-            if os.environ.get("CRIS_MODULE_REPLAY", "graph") == "cmdlist":
+            mode = os.environ.get("CRIS_MODULE_REPLAY", "graph")
+            st = dict(inputs=capture.stage(None, (img, word, mask), img.device), bwd=None,
+                      seed=torch.zeros(1, dtype=torch.int32, device=img.device),
+                      gscale=torch.ones(1, dtype=torch.float32, device=img.device))
+            if mode == "cmdlist":
                 # host command lists instead of HIP graphs: this call RUNS the forward while recording it
-                st = self._record_forward(img, word, mask, seed)
+                st["seed"].fill_(_seed_word(seed))
+                self._build_programs(st, mode, capture.shared_pool(mode), xchg, ("fwd",))
                 self._graphs[key] = st
                 return st
             try:
-                st = self._capture_graphs(img, word, mask, xchg)
+                self._build_programs(st, mode, capture.shared_pool(mode), xchg, ("fwd", "bwd"))
             except Exception as ex:              # noqa: BLE001 - fall back to the eager schedule, say why once
                 self.graph_error = repr(ex)
                 torch.cuda.synchronize()
-                eng.seed_dev = None
                 return None
             self._graphs[key] = st
         if st.get("bwd") is None:
@@ -475,10 +484,8 @@ class CRIS(nn.Module):
         if not getattr(self, "_replay_repacks", True) and not eng.packs_current:
             eng.repack_weights()                                             # (weights changed outside the bound optimizer)
             eng.packs_current = True
-        st["img"].copy_(img, non_blocking=True)
-        st["word"].copy_(word, non_blocking=True)
-        st["mask"].copy_(mask, non_blocking=True)
-        st["seed"].fill_(((int(seed) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000)     # the uint32 seed's bit pattern in the int32 word
+        capture.stage(st["inputs"], (img, word, mask), img.device)
+        st["seed"].fill_(_seed_word(seed))
         st["fwd"].replay()
         return st
 
@@ -503,71 +510,29 @@ class CRIS(nn.Module):
             self._engine.packs_current = False          # the bf16 operand copies no longer match the parameters
         return r
 
-    def _record_forward(self, img, word, mask, seed):
-        """CRIS_MODULE_REPLAY=cmdlist: the step's launches as host command lists (hip.CommandList) instead of two HIP graphs -
-        every library call of one executed forward (here) and backward (_record_backward, from the first backward of the
-        shape) is recorded with its arguments; all buffers come from a private memory pool that stays reserved.  A replay costs
-        ~3 us of host time per launch but the first kernel starts at once - under a loop that synchronises every step
-        (engine/engine.py:67-69) a graph launch's latency is paid twice per step and cannot be hidden by running ahead."""
-        from .. import hip
+    def _build_programs(self, st, mode, pool, xchg, parts):
+        """Build the `parts` ("fwd": forward + loss, "bwd": backward + gradient export) of the shape state `st` as `mode`
+        programs over `pool` (capture.build), reading the seed word st["seed"] and GradScaler's factor st["gscale"].  Graph
+        mode builds both here, next to each other on this thread and stream.  Command-list mode (CRIS_MODULE_REPLAY=cmdlist)
+        runs the forward while recording it and the backward at the first backward of the shape, over the forward's pool: a
+        replay costs ~3 us of host time per launch but the first kernel starts at once - under a loop that synchronises every
+        step (engine/engine.py:67-69) a graph launch's latency is paid twice per step and cannot be hidden by running ahead."""
         eng = self._engine
-        st = dict(img=img.clone(), word=word.clone(), mask=mask.clone(),
-                  seed=torch.zeros(1, dtype=torch.int32, device=img.device), gscale=torch.ones(1, dtype=torch.float32, device=img.device))
-        st["seed"].fill_(((int(seed) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000)
-        st["pool"] = torch.cuda.MemPool()
-        fwd = hip.CommandList()
-        eng.seed_dev = st["seed"]
-        self._prepare_packs_for_capture()
-        try:
-            with torch.cuda.use_mem_pool(st["pool"]):
-                hip.RECORDER = fwd
-                try:
-                    pred, msk, loss = self._training_forward(st["img"], st["word"], st["mask"], 0)
-                finally:
-                    hip.RECORDER = None
-        finally:
-            eng.seed_dev = None
-        st.update(fwd=fwd, bwd=None, pred=pred, msk=msk, loss=loss)
-        return st
-
-    def _record_backward(self, st, xchg=None):
-        from .. import hip
-        eng = self._engine
-        bwd = hip.CommandList()
         eng.seed_dev = st["seed"]
         try:
-            with torch.cuda.use_mem_pool(st["pool"]):
-                hip.RECORDER = bwd
-                try:
+            if "fwd" in parts:
+                self._prepare_packs_for_capture()
+                # (capture.py: thread_local mode + drained c10d watchdog - DistributedDataParallel's all-reduces of the previous
+                # step are still on the watchdog's list when the second step captures)
+                st["fwd"], (st["pred"], st["msk"], st["loss"]) = capture.build(
+                    mode, lambda: self._training_forward(*st["inputs"], 0), pool=pool)
+            if "bwd" in parts:
+                def backward():
                     self._backward_and_exchange(st["gscale"], xchg)
-                    grads = self._export_grads()
-                finally:
-                    hip.RECORDER = None
+                    return self._export_grads()
+                st["bwd"], st["grads"] = capture.build(mode, backward, pool=pool, drain=False)
         finally:
             eng.seed_dev = None
-        st.update(bwd=bwd, grads=grads)
-
-    def _capture_graphs(self, img, word, mask, xchg=None):
-        eng = self._engine
-        st = dict(img=img.clone(), word=word.clone(), mask=mask.clone(),
-                  seed=torch.zeros(1, dtype=torch.int32, device=img.device), gscale=torch.ones(1, dtype=torch.float32, device=img.device))
-        from .. import capture
-        pool = torch.cuda.graph_pool_handle()
-        fwd, bwd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        eng.seed_dev = st["seed"]
-        try:
-            self._prepare_packs_for_capture()
-            # (capture.py: thread_local mode + drained c10d watchdog - DistributedDataParallel's all-reduces of the previous
-            # step are still on the watchdog's list when the second step captures)
-            with capture.graph(fwd, pool=pool):
-                pred, msk, loss = self._training_forward(st["img"], st["word"], st["mask"], 0)
-            with capture.graph(bwd, pool=pool, drain=False):
-                self._backward_and_exchange(st["gscale"], xchg)
-                grads = self._export_grads()
-        finally:
-            eng.seed_dev = None
-        st.update(fwd=fwd, bwd=bwd, pred=pred, msk=msk, loss=loss, grads=grads)
-        return st
 
     def forward(self, img, word, mask=None):
         """img: b, 3, h, w ; word: b, words ; mask: b, 1, h, w   (reference model/segmenter.py:29-35)"""

@@ -24,7 +24,7 @@ from typing import Optional
 
 import torch
 
-from . import debug, ops
+from . import capture, debug, ops
 from .arch import ClipSpec, HeadSpec
 from .engine import Engine
 
@@ -136,7 +136,6 @@ class NativeTrainer:
         self.use_graph = launch != "eager"
         self._graph = None
         self._cmds = None
-        self._pool = None
         self._static = None
         self._eager_steps = 0
         self.graph_error = None
@@ -213,56 +212,43 @@ class NativeTrainer:
         self._host_steps += 1
         if self._peer_check_every > 0 and self._host_steps % self._peer_check_every == 0 and getattr(self.comm, "p2p", None) is not None:
             self.check_peer_timeout()
+        self._check_equal_batch(img.shape[0])
         if not self.use_graph or seed is not None or ops.KERNEL_TIMER is not None:
-            self._check_equal_batch(img.shape[0])
             loss, _, _ = self._step_body(img, word, mask, seed)
             return loss, self.metric
         key = (tuple(img.shape), tuple(word.shape), tuple(mask.shape))
-        self._check_equal_batch(img.shape[0])
         if self._static is not None and self._static[0] != key:
             self._graph, self._cmds, self._static, self._eager_steps = None, None, None, 0      # new shapes: new schedule
+        self._static = (key, capture.stage(self._static and self._static[1], (img, word, mask), self.device))
         if self._graph is None and self._cmds is None:
+            def body():
+                return self._step_body(*self._static[1], None)
             if self._eager_steps < 1:
                 # first step with these shapes runs eagerly: constant tables get uploaded, the allocator warms up
                 self._eager_steps += 1
-                self._static = (key, img.clone(), word.clone(), mask.clone())
-                loss, _, _ = self._step_body(self._static[1], self._static[2], self._static[3], None)
-                return loss, self.metric
+                return body()[0], self.metric
+            if self.launch == "graph":
+                err = None
+                try:
+                    # (capture.py: thread_local mode + a drained c10d watchdog - the eager first step left collectives of
+                    # two communicators behind whose end events the watchdog thread is still polling)
+                    self._graph, (self._loss, *self._keep) = capture.build("graph", body, device=self.device)
+                except Exception as ex:          # noqa: BLE001 - e.g. a collective that cannot be captured
+                    err = repr(ex)
+                if self.comm.world > 1:          # the ranks must agree on the launch mode
+                    err = next((x for x in self.comm.all_gather_object(err) if x), None)
+                if err is not None:
+                    self.graph_error, self._graph = err, None
+                    torch.cuda.synchronize(self.device)
+                    self.launch = "cmdlist" if self.comm.world > 1 else "eager"
+                    self.use_graph = self.launch == "cmdlist"
+            if self.launch == "eager":
+                return body()[0], self.metric
             if self.launch == "cmdlist":
-                _, s_img, s_word, s_mask = self._static
-                s_img.copy_(img, non_blocking=True)
-                s_word.copy_(word, non_blocking=True)
-                s_mask.copy_(mask, non_blocking=True)
-                return self._record(), self.metric            # this call executes the step while recording it
-            err = None
-            try:
-                self._capture()
-            except Exception as ex:              # noqa: BLE001 - e.g. a collective that cannot be captured
-                err = repr(ex)
-            if self.comm.world > 1:              # the ranks must agree on the launch mode
-                err = next((x for x in self.comm.all_gather_object(err) if x), None)
-            if err is not None:
-                self.graph_error, self._graph = err, None
-                torch.cuda.synchronize(self.device)
-                if self.comm.world > 1:
-                    self.launch = "cmdlist"
-                    _, s_img, s_word, s_mask = self._static
-                    s_img.copy_(img, non_blocking=True)
-                    s_word.copy_(word, non_blocking=True)
-                    s_mask.copy_(mask, non_blocking=True)
-                    return self._record(), self.metric
-                self.use_graph = False
-                self.launch = "eager"
-                loss, _, _ = self._step_body(img, word, mask, None)
-                return loss, self.metric
-        _, s_img, s_word, s_mask = self._static
-        s_img.copy_(img, non_blocking=True)
-        s_word.copy_(word, non_blocking=True)
-        s_mask.copy_(mask, non_blocking=True)
-        if self._graph is not None:
-            self._graph.replay()
-        else:
-            self._cmds.replay()
+                # this call executes the step while recording it; its buffers come from the list's own MemPool
+                self._cmds, (self._loss, *self._keep) = capture.build("cmdlist", body)
+                return self._loss, self.metric
+        (self._graph if self._graph is not None else self._cmds).replay()
         return self._loss, self.metric
 
     def _check_equal_batch(self, b):
@@ -273,32 +259,6 @@ class NativeTrainer:
             if any(x != sizes[0] for x in sizes):
                 raise ValueError("per-rank batch sizes differ across ranks (%s): SyncBN statistics assume equal shards" % (sizes,))
             self._checked_batch = b
-
-    def _capture(self):
-        from . import capture
-        _, s_img, s_word, s_mask = self._static
-        g = torch.cuda.CUDAGraph()
-        # thread_local capture mode + a drained c10d watchdog (capture.py): the eager first step left collectives of two
-        # communicators behind whose end events the watchdog thread is still polling
-        with capture.graph(g, device=self.device):
-            loss, pred, msk = self._step_body(s_img, s_word, s_mask, None)
-        self._graph, self._loss, self._keep = g, loss, (pred, msk)
-
-    def _record(self):
-        """Execute one step through the Python schedule while recording it as a command list; every buffer it allocates
-        comes from a private MemPool that stays reserved, so the recorded addresses remain valid for the replays."""
-        from . import hip
-        _, s_img, s_word, s_mask = self._static
-        self._pool = torch.cuda.MemPool()
-        rec = hip.CommandList()
-        with torch.cuda.use_mem_pool(self._pool):
-            hip.RECORDER = rec
-            try:
-                loss, pred, msk = self._step_body(s_img, s_word, s_mask, None)
-            finally:
-                hip.RECORDER = None
-        self._cmds, self._loss, self._keep = rec, loss, (pred, msk)
-        return loss
 
     # ------------------------------------------------------------------------------------------------
     # checkpointing (reference train.py:159-174,192-207: {'epoch', 'cur_iou', 'best_iou', 'state_dict', 'optimizer', 'scheduler'})
