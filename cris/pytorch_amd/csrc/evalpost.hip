@@ -109,16 +109,18 @@ __global__ __launch_bounds__(256) void warp_affine_cubic_kernel(const float* __r
     }
 }
 
-extern "C" int cris_warp_affine_cubic(const float* src, int H, int W, const double* mat, int w_out, int h_out, float border, float* dst,
-                                      void* stream) {
-    CRIS_CHECK_ARG(src && mat && dst && H > 0 && W > 0 && w_out > 0 && h_out > 0, "bad args");
-    ep_warp_args a;
-    // cv::invertAffineTransform (the caller passes the matrix cv2.warpAffine is given, without WARP_INVERSE_MAP)
-    double D = mat[0] * mat[4] - mat[1] * mat[3];
-    D = D != 0.0 ? 1.0 / D : 0.0;
-    const double A11 = mat[4] * D, A22 = mat[0] * D, A12 = -mat[1] * D, A21 = -mat[3] * D;
-    a.m[0] = A11; a.m[1] = A12; a.m[2] = -A11 * mat[2] - A12 * mat[5];
-    a.m[3] = A21; a.m[4] = A22; a.m[5] = -A21 * mat[2] - A22 * mat[5];
+// Host side of both warp launchers: cv::invertAffineTransform in double (the caller passes the matrix cv2.warpAffine is given,
+// without WARP_INVERSE_MAP) into m (skipped when mat is NULL: the batched launcher's descriptors hold inverted matrices already,
+// made by cris_eval_desc_fill through this same function), and the 32 x 4 table of cv::interpolateCubic.
+static void ep_warp_setup(const double* mat, double* m, float (*tab)[4]) {
+    if (mat) {
+        double D = mat[0] * mat[4] - mat[1] * mat[3];
+        D = D != 0.0 ? 1.0 / D : 0.0;
+        const double A11 = mat[4] * D, A22 = mat[0] * D, A12 = -mat[1] * D, A21 = -mat[3] * D;
+        m[0] = A11; m[1] = A12; m[2] = -A11 * mat[2] - A12 * mat[5];
+        m[3] = A21; m[4] = A22; m[5] = -A21 * mat[2] - A22 * mat[5];
+    }
+    if (!tab) return;
     const volatile float A = -0.75f;                            // (volatile: keep the float operations separate, no contraction)
     for (int i = 0; i < 32; ++i) {
         const volatile float t = (float)i / 32.0f;
@@ -128,8 +130,15 @@ extern "C" int cris_warp_affine_cubic(const float* src, int H, int W, const doub
         u = 1.0f - t;
         q = (A + 2.0f) * u; q = q - (A + 3.0f); q = q * u; q = q * u; c2 = q + 1.0f;
         q = 1.0f - c0; q = q - c1; q = q - c2;
-        a.tab[i][0] = c0; a.tab[i][1] = c1; a.tab[i][2] = c2; a.tab[i][3] = q;
+        tab[i][0] = c0; tab[i][1] = c1; tab[i][2] = c2; tab[i][3] = q;
     }
+}
+
+extern "C" int cris_warp_affine_cubic(const float* src, int H, int W, const double* mat, int w_out, int h_out, float border, float* dst,
+                                      void* stream) {
+    CRIS_CHECK_ARG(src && mat && dst && H > 0 && W > 0 && w_out > 0 && h_out > 0, "bad args");
+    ep_warp_args a;
+    ep_warp_setup(mat, a.m, a.tab);
     hipLaunchKernelGGL(warp_affine_cubic_kernel, dim3(cris_grid_1d((long)w_out * h_out, 256)), dim3(256), 0, (hipStream_t)stream, src, H, W,
                        a, w_out, h_out, border, dst);
     CRIS_LAUNCH_CHECK();
@@ -159,6 +168,120 @@ __global__ __launch_bounds__(256) void threshold_iou_kernel(const float* __restr
 extern "C" int cris_threshold_iou(const float* pred, const float* mask, long n, float thr, int* counts, void* stream) {
     CRIS_CHECK_ARG(pred && mask && counts && n > 0, "bad args");
     hipLaunchKernelGGL(threshold_iou_kernel, dim3(cris_grid_1d(n, 256, 512)), dim3(256), 0, (hipStream_t)stream, pred, mask, n, thr, counts);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- one launch per batch: warp + threshold + counts for n ragged samples (engine.py:108-124 / :166-190 as one kernel) ----
+// blockIdx.y = descriptor, blockIdx.x strides over that sample's groups of 4 consecutive x positions (one mask dword each).
+// The per-pixel value is warp_affine_cubic_kernel's, operation for operation (same fixed-point coordinates, same 16-tap
+// accumulation order); it is compared with thr in a register and never stored.  Integer sums: wave shuffle, then the 4 waves of
+// the block through LDS, then one atomicAdd pair per block (exact, order-free).
+struct ep_cubic_tab {
+    float tab[32][4];
+};
+
+__global__ __launch_bounds__(256) void eval_iou_batch_kernel(const float* __restrict__ probs, int H, int W,
+                                                             const cris_eval_desc* __restrict__ descs,
+                                                             const unsigned char* __restrict__ masks, const ep_cubic_tab t, float thr,
+                                                             float border, int* __restrict__ counts, unsigned char* __restrict__ out) {
+    __shared__ float tab[32][4];
+    __shared__ int red[2][4];
+    if (threadIdx.x < 128) tab[threadIdx.x >> 2][threadIdx.x & 3] = t.tab[threadIdx.x >> 2][threadIdx.x & 3];
+    __syncthreads();
+    const cris_eval_desc d = descs[blockIdx.y];
+    const float* __restrict__ src = probs + (size_t)d.map * H * W;
+    const unsigned char* __restrict__ mrow = masks + d.mask_off;
+    const int gpr = d.pitch >> 2;                                  // groups per row (the pitch is a multiple of 4)
+    const long total = (long)gpr * d.h_out;
+    const double AB = (double)(1 << EP_AB_BITS);
+    const int round_delta = (1 << EP_AB_BITS) / (1 << EP_INTER_BITS) / 2;
+    int inter = 0, uni = 0;
+    for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long)gridDim.x * blockDim.x) {
+        const int y = (int)(g / gpr), x0 = (int)(g % gpr) * 4;
+        const size_t boff = (size_t)y * d.pitch + x0;
+        const unsigned int mword = *reinterpret_cast<const unsigned int*>(mrow + boff);
+        const long X0 = (long)rint(ep_dmul(ep_dadd(ep_dmul(d.m[1], (double)y), d.m[2]), AB)) + round_delta;
+        const long Y0 = (long)rint(ep_dmul(ep_dadd(ep_dmul(d.m[4], (double)y), d.m[5]), AB)) + round_delta;
+        unsigned int oword = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = x0 + j;
+            if (x < d.w_out) {                                     // (lanes past w_out: padding bytes, not counted)
+                const long adelta = (long)rint(ep_dmul(ep_dmul(d.m[0], (double)x), AB)), bdelta = (long)rint(ep_dmul(ep_dmul(d.m[3], (double)x), AB));
+                const long Xq = (X0 + adelta) >> (EP_AB_BITS - EP_INTER_BITS), Yq = (Y0 + bdelta) >> (EP_AB_BITS - EP_INTER_BITS);
+                const int sx = (int)(Xq >> EP_INTER_BITS) - 1, sy = (int)(Yq >> EP_INTER_BITS) - 1;
+                const int fx = (int)(Xq & 31), fy = (int)(Yq & 31);
+                float acc = 0.f;
+#pragma unroll
+                for (int ky = 0; ky < 4; ++ky) {
+                    const int yy = sy + ky;
+#pragma unroll
+                    for (int kx = 0; kx < 4; ++kx) {
+                        const int xx = sx + kx;
+                        const bool inside = yy >= 0 && yy < H && xx >= 0 && xx < W;
+                        const float v = inside ? src[(size_t)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)] : border;
+                        const float wgt = ep_mul(tab[fy][ky], tab[fx][kx]);
+                        acc = ep_add(acc, ep_mul(v, wgt));
+                    }
+                }
+                const bool p = acc > thr, m = ((mword >> (8 * j)) & 0xffu) != 0u;
+                inter += (p && m) ? 1 : 0;
+                uni += (p || m) ? 1 : 0;
+                oword |= p ? (0xffu << (8 * j)) : 0u;
+            }
+        }
+        if (out) *reinterpret_cast<unsigned int*>(out + d.out_off + boff) = oword;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        inter += __shfl_xor(inter, o, 64);
+        uni += __shfl_xor(uni, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = inter;
+        red[1][threadIdx.x >> 6] = uni;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(counts + 2 * (size_t)d.row, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+        atomicAdd(counts + 2 * (size_t)d.row + 1, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+    }
+}
+
+extern "C" int cris_eval_desc_fill(cris_eval_desc* desc, const double* mat, int w_out, int h_out, int map, long mask_off, int pitch,
+                                   long out_off, int row) {
+    CRIS_CHECK_ARG(desc && mat, "bad args");
+    ep_warp_setup(mat, desc->m, nullptr);
+    desc->w_out = w_out; desc->h_out = h_out; desc->map = map; desc->row = row;
+    desc->mask_off = mask_off; desc->out_off = out_off; desc->pitch = pitch; desc->pad_ = 0;
+    return 0;
+}
+
+extern "C" int cris_eval_iou_batch(const float* probs, int P, int H, int W, const cris_eval_desc* descs_host,
+                                   const cris_eval_desc* descs_dev, int n, const unsigned char* masks, size_t mask_bytes, float thr,
+                                   float border, int* counts, int count_rows, unsigned char* out_masks, size_t out_bytes, void* stream) {
+    CRIS_CHECK_ARG(probs && descs_host && descs_dev && masks && counts, "null operand");
+    CRIS_CHECK_ARG(P > 0 && H > 0 && W > 0 && n > 0 && n <= 65535 && count_rows > 0, "bad sizes");
+    CRIS_CHECK_ARG(((uintptr_t)masks & 3) == 0 && ((uintptr_t)out_masks & 3) == 0, "mask buffers must be 4-byte aligned");
+    long most = 0;
+    for (int i = 0; i < n; ++i) {                                  // every address the kernel forms is checked here, on the host copy
+        const cris_eval_desc& d = descs_host[i];
+        CRIS_CHECK_ARG(d.w_out > 0 && d.h_out > 0 && (long)d.w_out * d.h_out < (1L << 31), "descriptor: bad output size");
+        CRIS_CHECK_ARG(d.map >= 0 && d.map < P && d.row >= 0 && d.row < count_rows, "descriptor: map / row out of range");
+        CRIS_CHECK_ARG(d.pitch >= d.w_out && (d.pitch & 3) == 0 && d.pitch - d.w_out < (1 << 20), "descriptor: the pitch must be a multiple of 4, >= w_out");
+        const size_t bytes = (size_t)d.pitch * d.h_out;
+        CRIS_CHECK_ARG(d.mask_off >= 0 && (d.mask_off & 3) == 0 && (size_t)d.mask_off + bytes <= mask_bytes, "descriptor: mask outside the buffer");
+        if (out_masks)
+            CRIS_CHECK_ARG(d.out_off >= 0 && (d.out_off & 3) == 0 && (size_t)d.out_off + bytes <= out_bytes, "descriptor: output outside the buffer");
+        const long groups = (long)(d.pitch >> 2) * d.h_out;
+        if (groups > most) most = groups;
+    }
+    ep_cubic_tab t;
+    ep_warp_setup(nullptr, nullptr, t.tab);
+    const int cap = 2048 / n > 8 ? 2048 / n : 8;                   // ~2048 blocks in all, grid-stride for the rest
+    hipLaunchKernelGGL(eval_iou_batch_kernel, dim3(cris_grid_1d(most, 256, cap), n), dim3(256), 0, (hipStream_t)stream, probs, H, W,
+                       descs_dev, masks, t, thr, border, counts, out_masks);
     CRIS_LAUNCH_CHECK();
     return 0;
 }

@@ -7,7 +7,11 @@
     pred  = pred > 0.35 ; iou = sum(pred & mask) / (sum(pred | mask) + 1e-6)                        :117-123
 
 The reference copies every prediction to the host and warps it with cv2; here all four steps are kernels of
-libcris_hip.so (csrc/evalpost.hip) and only the two integer counts per sample come back.  There is no CPU fallback."""
+libcris_hip.so (csrc/evalpost.hip) and only the two integer counts per sample come back.  There is no CPU fallback.
+
+`validate_batch` is the per-sample form (one warp and one count launch per sample, float masks).  `iou_batch` is the batched
+form that evaluate.Evaluator drives: steps 3-4 for a whole ragged batch in ONE launch, uint8 masks and the descriptor table
+packed into one pinned buffer (`EvalStaging`), the warped map never written, counts accumulated in a table for the whole pass."""
 import ctypes as C
 
 import numpy as np
@@ -65,3 +69,100 @@ def validate_batch(logits, in_size, mats, ori_sizes, masks, thr=0.35):
         counts.append(iou_counts(p, m, thr))
     c = torch.stack(counts).cpu().numpy().astype(np.float64)
     return [float(i / (u + 1e-6)) for i, u in c]
+
+
+class EvalStaging:
+    """One batch of `iou_batch` work on the host and its twin on the device: the descriptor table (hip.EvalDesc) followed by the
+    packed uint8 masks, in ONE host buffer (pinned when the device is a GPU) that `upload()` sends with one asynchronous copy.
+    Mask rows are padded with zeros to a pitch that is a multiple of 4 (the kernel reads one dword per 4 pixels); every mask
+    starts on a 16-byte boundary.  Several descriptors may name one mask (the expressions of one image).  `device=None` keeps
+    the host half only (packing is host arithmetic)."""
+
+    ALIGN = 16
+
+    def __init__(self, device=None, max_descs=64, mask_bytes=1 << 20):
+        self.device = None if device is None else torch.device(device)
+        self.host = self.dev = self.event = None
+        self.n = self.mask_bytes = self.out_bytes = 0
+        self._reserve(max_descs, mask_bytes)
+
+    @staticmethod
+    def _up(v, a):
+        return (int(v) + a - 1) // a * a
+
+    def _reserve(self, max_descs, mask_bytes):
+        self.wait()
+        self.max_descs, self.mask_cap = int(max_descs), self._up(mask_bytes, self.ALIGN)
+        self.mask_base = self._up(self.max_descs * C.sizeof(hip.EvalDesc), self.ALIGN)
+        pin = self.device is not None and self.device.type == "cuda"
+        self.host = torch.zeros(self.mask_base + self.mask_cap, dtype=torch.uint8, pin_memory=pin)
+        self.dev = None if self.device is None else torch.empty_like(self.host, device=self.device)
+        self.descs = (hip.EvalDesc * self.max_descs).from_address(self.host.data_ptr())
+        self._bytes = self.host.numpy()
+
+    def wait(self):
+        """until the last upload has left the host buffer (it is about to be overwritten)"""
+        if self.event is not None:
+            self.event.synchronize()
+            self.event = None
+
+    def pack(self, masks, descs):
+        """masks: uint8 [h, w] CPU tensors / arrays.  descs: (mat, mask index, map index, count row) per descriptor, `mat` the
+        2x3 matrix cv2.warpAffine is given (param['inverse']); the output size of a descriptor is its mask's size."""
+        shapes = [(int(m.shape[0]), int(m.shape[1])) for m in masks]
+        pitches = [self._up(w, 4) for _, w in shapes]
+        need = sum(self._up(p * h, self.ALIGN) for p, (h, _) in zip(pitches, shapes))
+        if len(descs) > self.max_descs or need > self.mask_cap:
+            self._reserve(max(len(descs), self.max_descs), max(need + need // 4, self.mask_cap))
+        self.wait()
+        offs, off = [], 0
+        for m, p, (h, w) in zip(masks, pitches, shapes):
+            rows = self._bytes[self.mask_base + off:self.mask_base + off + p * h].reshape(h, p)
+            rows[:, :w] = m.numpy() if torch.is_tensor(m) else np.asarray(m, dtype=np.uint8)
+            rows[:, w:] = 0
+            offs.append(off)
+            off += self._up(p * h, self.ALIGN)
+        self.mask_bytes, out_off = off, 0
+        for i, (mat, mi, mp, row) in enumerate(descs):
+            m = np.ascontiguousarray(np.asarray(mat, dtype=np.float64).reshape(6))
+            h, w = shapes[mi]
+            hip.call("cris_eval_desc_fill", C.addressof(self.descs[i]), m.ctypes.data_as(C.c_void_p), w, h, int(mp), offs[mi], pitches[mi],
+                     out_off, int(row))
+            out_off += self._up(pitches[mi] * h, self.ALIGN)
+        self.n, self.out_bytes = len(descs), out_off
+        return self
+
+    def upload(self):
+        """one asynchronous copy of the descriptor table and the masks (the used prefix of the buffer) on the current stream"""
+        end = self.mask_base + self.mask_bytes
+        self.dev[:end].copy_(self.host[:end], non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record()
+        return self
+
+    @property
+    def masks(self):
+        """the packed masks on the device (after upload())"""
+        return self.dev[self.mask_base:self.mask_base + self.mask_bytes]
+
+
+def iou_batch(probs, descs, masks_u8, counts, row0, thr=0.35, out_masks=None, border=0.0):
+    """ONE launch for a whole batch (cris_eval_iou_batch): for every descriptor of `descs` (an uploaded EvalStaging) the inverse
+    warp of probs[map] to the original size, the threshold and counts[row0 + row] += (intersection, union) against its mask in
+    `masks_u8` (device uint8, the staging's packed masks).  probs: [P, H, W] cuda fp32 (sigmoid_upsample); counts: [R, 2] cuda
+    int32, zeroed by the caller once per pass; out_masks: optional device uint8 buffer of descs.out_bytes that receives
+    (warp > thr) * 255 per descriptor (row pitch of its mask, descriptor i at descs.descs[i].out_off)."""
+    if probs.device.type != "cuda":
+        raise RuntimeError("evalpost runs on the GPU only (no CPU fallback)")
+    if probs.dim() != 3 or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise ValueError("iou_batch: probs must be contiguous fp32 [P, H, W]")
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != 2 or not counts.is_contiguous() or not 0 <= row0 < counts.shape[0]:
+        raise ValueError("iou_batch: counts must be contiguous int32 [R, 2] and row0 inside it")
+    if masks_u8.dtype != torch.uint8 or not masks_u8.is_contiguous():
+        raise ValueError("iou_batch: masks_u8 must be a contiguous uint8 buffer")
+    if out_masks is not None and (out_masks.dtype != torch.uint8 or not out_masks.is_contiguous() or out_masks.numel() < descs.out_bytes):
+        raise ValueError("iou_batch: out_masks must be a contiguous uint8 buffer of at least descs.out_bytes")
+    P, H, W = probs.shape
+    hip.call("cris_eval_iou_batch", ptr(probs), P, H, W, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n, ptr(masks_u8),
+             masks_u8.numel(), float(thr), float(border), counts.data_ptr() + 8 * int(row0), counts.shape[0] - int(row0),
+             ptr(out_masks), 0 if out_masks is None else out_masks.numel(), _stream())

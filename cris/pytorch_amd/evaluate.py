@@ -1,0 +1,190 @@
+"""A whole dataset split through the model on the GPU - the bodies of the reference's `validate` and `inference`
+(reference engine/engine.py:90-143, :146-215) behind the same results: `(iou, prec)` with `prec` keyed 'Pr@50' ... 'Pr@90'.
+
+    validate:  first sentence of every record, batches of `batch_size`                         engine.py:95-124
+    inference: every sentence of every record; the images of a batch share one visual pass      engine.py:152-190
+    metrics:   iou_i = inter / (union + 1e-6), IoU = mean, Pr@X = mean(iou_i > X)               engine.py:125-143, :199-215
+
+Per batch: RecordPipeline (JPEG decode + letter-box on the GPU), the model, `evalpost.sigmoid_upsample`, and ONE launch of
+`evalpost.iou_batch` that warps every prediction back to its original size, thresholds it and adds (intersection, union) to the
+sample's row of a device table.  The masks come from the records' own `mask` bytes (tools/folder2lmdb.py:49-50 stores the file
+`mask_dir` names), packed as uint8 next to the descriptors in a pinned buffer: one asynchronous copy per batch.  The table is
+read ONCE, after the last batch - no batch waits for the host (a `visualize` callback needs each batch's result and does wait).
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import evalpost, pngdec
+
+PR_KEYS = tuple("Pr@%d" % (t * 10) for t in range(5, 10))
+
+
+def pr_thresholds():
+    """the reference's `torch.arange(0.5, 1.0, 0.1)`: FLOAT32 values, which its float64-tensor > float32-scalar comparison
+    widens to double (0.6f = 0.60000002384..., so an IoU of exactly 0.6 does not count for Pr@60)"""
+    return [float(t) for t in torch.arange(0.5, 1.0, 0.1)]
+
+
+def metrics(counts):
+    """counts: [n, 2] integers (intersection, union) per sample -> (iou, prec, per_sample) as the reference computes them on
+    the host in float64 (engine.py:123-143): iou_i = inter / (union + 1e-6), iou = mean(iou_i), prec['Pr@X'] =
+    mean(iou_i > X) with the float32 thresholds of pr_thresholds() (the reference's `.float().mean()`: a float32 quotient)."""
+    c = np.asarray(counts, dtype=np.float64).reshape(-1, 2)
+    if c.shape[0] == 0:
+        raise ValueError("metrics: no samples")
+    per = c[:, 0] / (c[:, 1] + 1e-6)
+    n = np.float32(per.shape[0])
+    prec = {k: float(np.float32(int((per > t).sum())) / n) for k, t in zip(PR_KEYS, pr_thresholds())}
+    return float(per.mean()), prec, per
+
+
+def shard_indices(n, rank, world):
+    """the indices `DistributedSampler(range(n), world, rank, shuffle=False)` yields: the list padded by wrapping around to a
+    multiple of `world`, then every world-th entry from `rank` on (so the gathered metrics count the wrapped samples twice,
+    as the reference's do)"""
+    if not 0 <= rank < world or n <= 0:
+        raise ValueError("shard_indices: need n > 0 and 0 <= rank < world")
+    idx = list(range(n))
+    total = math.ceil(n / world) * world
+    pad = total - n
+    idx += (idx * math.ceil(pad / n))[:pad]
+    return idx[rank:total:world]
+
+
+def gather_counts(counts, group=None):
+    """`concat_all_gather` of the per-rank count tables (rank order, duplicates included) when a process group is given or
+    torch.distributed is initialised; otherwise `counts` itself.  counts: CPU integer tensor [n, 2], n equal on every rank
+    (shard_indices)."""
+    import torch.distributed as dist
+    if group is None and not (dist.is_available() and dist.is_initialized()):
+        return counts
+    world = dist.get_world_size(group)
+    if world == 1:
+        return counts
+    dev = "cuda" if "nccl" in str(dist.get_backend(group)).lower() else "cpu"
+    mine = counts.to(dev).contiguous()
+    parts = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(parts, mine, group=group)
+    return torch.cat(parts, 0).cpu()
+
+
+def _pad_to(n, multiple):
+    return (n + multiple - 1) // multiple * multiple
+
+
+def plan_validate(masks, inverses, row0=0):
+    """(masks, descriptors) of one validate batch for EvalStaging.pack: sample b reads probability map b and its own mask and
+    counts into row row0 + b.  A padded batch passes its REAL samples only: padding gets no descriptor."""
+    return masks, [(inv, b, b, row0 + b) for b, inv in enumerate(inverses)]
+
+
+def plan_inference(masks, inverses, sents_per_image, multiple=8):
+    """One inference batch: image i has sents_per_image[i] expressions.  Returns (image index of every expression padded to a
+    multiple of `multiple` by repeating the last one, masks, descriptors): expression k reads map k, the ONE mask of its image
+    and counts into row k; the padding gets no descriptor."""
+    index = [i for i, k in enumerate(sents_per_image) for _ in range(k)]
+    descs = [(inverses[i], i, k, k) for k, i in enumerate(index)]
+    return index + [index[-1]] * (_pad_to(len(index), multiple) - len(index)), masks, descs
+
+
+class Evaluator:
+    """`Evaluator(model, pipeline, thr=0.35)`: model - any callable `(img, word) -> logits [B, 1, h, w]` (an InferenceRunner, the
+    drop-in CRIS module in eval mode); when it also offers `segment(img, word, image_index)` or `segment_expressions`, `inference`
+    runs the visual encoder once per image.  pipeline - a RecordPipeline in mode "val" (validate) or "test" (inference).
+    `records` is anything indexable that yields record dicts (records.LmdbRecords, a list).  After a pass `per_sample` holds
+    this process's IoUs and `counts` its (intersection, union) table."""
+
+    RING = 3            # staging buffers in flight: a batch's host packing overlaps the copies of the two before it
+
+    def __init__(self, model, pipeline, thr=0.35):
+        self.model, self.pipe, self.thr = model, pipeline, float(thr)
+        self.device = pipeline.device
+        self._segment = getattr(model, "segment", None) or getattr(model, "segment_expressions", None)
+        self._ring = [evalpost.EvalStaging(self.device) for _ in range(self.RING)]
+        self._turn = 0
+        self.per_sample = self.counts = None
+
+    def _staging(self):
+        self._turn = (self._turn + 1) % self.RING
+        return self._ring[self._turn]
+
+    @staticmethod
+    def _masks(recs, params):
+        masks = [pngdec.decode_gray(r["mask"]) for r in recs]
+        for m, p in zip(masks, params):
+            if tuple(m.shape) != tuple(int(v) for v in p["ori_size"]):
+                raise ValueError("record %s: mask is %s, image %s" % (p["mask_dir"], tuple(m.shape), tuple(p["ori_size"])))
+        return masks
+
+    def _finish(self, table, n, group):
+        counts = gather_counts(table[:n].cpu(), group)             # the pass's one host read
+        iou, prec, per = metrics(counts.numpy())
+        self.counts = counts.numpy()
+        self.per_sample = per
+        return iou, prec
+
+    @torch.no_grad()
+    def validate(self, records, indices=None, batch_size=32, group=None):
+        if self.pipe.mode != "val":
+            raise ValueError("validate needs a RecordPipeline in mode 'val'")
+        indices = list(range(len(records))) if indices is None else [int(i) for i in indices]
+        if not indices:
+            raise ValueError("validate: no records")
+        table = torch.zeros(len(indices), 2, dtype=torch.int32, device=self.device)
+        for lo in range(0, len(indices), batch_size):
+            recs = [records[i] for i in indices[lo:lo + batch_size]]
+            img, word, params = self.pipe(recs)
+            n = len(recs)
+            if n < batch_size:                                     # short last batch: repeat its last sample, one graph shape
+                rep = torch.tensor(list(range(n)) + [n - 1] * (batch_size - n), device=self.device)
+                img, word = img[rep], word[rep]
+            st = self._staging().pack(*plan_validate(self._masks(recs, params), [p["inverse"] for p in params])).upload()
+            probs = evalpost.sigmoid_upsample(self.model(img, word), img.shape[-2], img.shape[-1])
+            evalpost.iou_batch(probs, st, st.masks, table, lo, self.thr)
+        return self._finish(table, len(indices), group)
+
+    @torch.no_grad()
+    def inference(self, records, indices=None, images_per_batch=8, visualize=None):
+        if self.pipe.mode != "test":
+            raise ValueError("inference needs a RecordPipeline in mode 'test'")
+        indices = list(range(len(records))) if indices is None else [int(i) for i in indices]
+        if not indices:
+            raise ValueError("inference: no records")
+        batches = [[records[i] for i in indices[lo:lo + images_per_batch]] for lo in range(0, len(indices), images_per_batch)]
+        total = sum(len(r["sents"]) for b in batches for r in b)
+        table = torch.zeros(total, 2, dtype=torch.int32, device=self.device)
+        row0 = 0
+        for recs in batches:
+            img, params = self.pipe(recs)
+            n = len(recs)
+            if n < images_per_batch:
+                rep = torch.tensor(list(range(n)) + [n - 1] * (images_per_batch - n), device=self.device)
+                img = img[rep]
+            sents = [s for p in params for s in p["sents"]]
+            index, masks, descs = plan_inference(self._masks(recs, params), [p["inverse"] for p in params],
+                                                 [len(p["sents"]) for p in params])
+            K = len(sents)
+            word = self.pipe.tok.tokenize(sents + [sents[-1]] * (len(index) - K), self.pipe.word_length, True)
+            word = word.to(self.device, non_blocking=True)
+            st = self._staging().pack(masks, descs).upload()
+            if self._segment is not None:
+                logits = self._segment(img, word, index)
+            else:
+                logits = self.model(img[torch.tensor(index, device=self.device)], word)
+            probs = evalpost.sigmoid_upsample(logits, img.shape[-2], img.shape[-1])
+            out = None if visualize is None else torch.empty(st.out_bytes, dtype=torch.uint8, device=self.device)
+            evalpost.iou_batch(probs, st, st.masks, table, row0, self.thr, out_masks=out)
+            if visualize is not None:
+                self._visualize(visualize, recs, sents, index, st, table[row0:row0 + K].cpu().numpy(), out.cpu().numpy())
+            row0 += K
+        return self._finish(table, total, None)
+
+    @staticmethod
+    def _visualize(callback, recs, sents, index, st, counts, out):
+        """callback(record, sentence, iou, uint8 mask [ori_h, ori_w] with values 0 / 255) per expression (engine.py:192-197)"""
+        for k, sent in enumerate(sents):
+            d = st.descs[k]
+            pred = out[d.out_off:d.out_off + d.pitch * d.h_out].reshape(d.h_out, d.pitch)[:, :d.w_out]
+            callback(recs[index[k]], sent, float(counts[k, 0] / (counts[k, 1] + 1e-6)), np.ascontiguousarray(pred))

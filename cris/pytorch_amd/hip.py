@@ -208,6 +208,11 @@ class SampleDesc(C.Structure):
     _fields_ = [("img", P), ("mask", P), ("H", I), ("W", I), ("inv", C.c_double * 6)]
 
 
+class EvalDesc(C.Structure):
+    _fields_ = [("m", C.c_double * 6), ("w_out", I), ("h_out", I), ("map", I), ("row", I),
+                ("mask_off", L), ("out_off", L), ("pitch", I), ("pad_", I)]
+
+
 class JpegInfo(C.Structure):
     _fields_ = [("width", I), ("height", I), ("ncomp", I), ("hmax", I), ("vmax", I), ("mcus_x", I), ("mcus_y", I),
                 ("restart_interval", I),
@@ -245,7 +250,7 @@ STRUCTS = {
     "cris_conv_gemm_fp8_params": ConvGemmFp8Params, "cris_pack_fp8_desc": PackFp8Desc,
     "cris_bn_apply_params": BnApplyParams, "cris_bn_bwd_params": BnBwdParams, "cris_ln_fwd_params": LnFwdParams,
     "cris_ln_bwd_params": LnBwdParams, "cris_sum_entry": SumEntry, "cris_sum_group": SumGroup, "cris_attn_params": AttnParams, "cris_adam_desc": AdamDesc, "cris_p2p_params": P2PParams, "cris_p2p_link": P2PLink, "cris_p2p_arena_params": P2PArenaParams, "cris_zero_ranges": ZeroRanges,
-    "cris_sample_desc": SampleDesc, "cris_jpeg_info": JpegInfo, "cris_jpeg_image": JpegImage,
+    "cris_sample_desc": SampleDesc, "cris_eval_desc": EvalDesc, "cris_jpeg_info": JpegInfo, "cris_jpeg_image": JpegImage,
 }
 
 # name -> (restype, argtypes); struct launchers take (struct*, stream)
@@ -339,6 +344,8 @@ _SIGS = {
     "cris_sigmoid_bicubic_up": (I, [P, I, I, I, I, I, P, P]),
     "cris_warp_affine_cubic": (I, [P, I, I, P, I, I, F, P, P]),
     "cris_threshold_iou": (I, [P, P, L, F, P, P]),
+    "cris_eval_desc_fill": (I, [P, P, I, I, I, L, I, L, I]),
+    "cris_eval_iou_batch": (I, [P, I, I, I, P, P, I, P, C.c_size_t, F, F, P, I, P, C.c_size_t, P]),
     "cris_preprocess_batch": (I, [P, I, I, I, P, P, P, P, P, P, P, P]),
     "cris_invert_affine": (I, [P, P]),
     "cris_remap_tables_u8": (I, [P, P]),
@@ -389,7 +396,7 @@ class HipLibraryError(RuntimeError):
     pass
 
 
-ABI_VERSION = 5      # == CRIS_ABI_VERSION of include/cris_hip.h (tests/test_abi.py compares the two)
+ABI_VERSION = 6      # == CRIS_ABI_VERSION of include/cris_hip.h (tests/test_abi.py compares the two)
 
 
 def load():

@@ -597,6 +597,16 @@ class CRIS(nn.Module):
         with torch.no_grad():
             return self._infer_runner(img).segment(img.float().contiguous(), word, image_index).clone()
 
+    def evaluator(self, pipeline, thr=0.35):
+        """The reference's `validate` / `inference` loops over a dataset split for this module (eval mode only):
+        `model.evaluator(records.RecordPipeline(size, word_len, device, mode="val")).validate(records)` -> (iou, prec).  An
+        evaluate.Evaluator bound to the eval forward and, for the test split's several sentences per image, to
+        segment_expressions."""
+        if self.training:
+            raise RuntimeError("evaluator is an inference object: put the model in eval() mode first")
+        from ..evaluate import Evaluator
+        return Evaluator(self, pipeline, thr=thr)
+
     def _infer_runner(self, img):
         """the inference runner on the engine's tensors, refolded when the parameters / running statistics changed"""
         from ..infer import InferenceRunner

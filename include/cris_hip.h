@@ -26,8 +26,8 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels */
-#define CRIS_ABI_VERSION 5
+ * mis-read them silently).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch */
+#define CRIS_ABI_VERSION 6
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
 int cris_sizeof(const char* struct_name);
@@ -481,6 +481,26 @@ int cris_warp_affine_cubic(const float* src, int H, int W, const double* mat, in
                            void* stream);
 /* counts[0] += #(pred > thr & mask), counts[1] += #(pred > thr | mask)  (engine.py:117-122); counts: 2 device ints */
 int cris_threshold_iou(const float* pred, const float* mask, long n, float thr, int* counts, void* stream);
+/* One launch per batch of the three steps above (warp + threshold + counts) for n ragged samples; the warped map is never written.
+ * A descriptor names its probability map, its mask (packed uint8 rows, zero-padded to a pitch that is a multiple of 4; several
+ * descriptors may share one mask: the expressions of one image) and its row of the count table.  Per pixel the value equals
+ * cris_warp_affine_cubic's bit for bit; a mask pixel counts when its byte is != 0.  counts[row][0..1] += (intersection, union);
+ * out_masks (may be NULL): (value > thr) * 255 as uint8 at out_off, with the mask's pitch, padding bytes zero.
+ * cris_eval_desc_fill (host) inverts `mat` (the matrix cv2.warpAffine is given) exactly as cris_warp_affine_cubic does.
+ * descs_host / descs_dev: the same n descriptors in host memory (checked here: sizes, offsets against mask_bytes / out_bytes,
+ * rows against count_rows) and in device memory (read by the kernel). */
+typedef struct {
+    double m[6];
+    int w_out, h_out;
+    int map, row;
+    long mask_off, out_off;
+    int pitch, pad_;
+} cris_eval_desc;
+int cris_eval_desc_fill(cris_eval_desc* desc, const double* mat, int w_out, int h_out, int map, long mask_off, int pitch,
+                        long out_off, int row);
+int cris_eval_iou_batch(const float* probs, int P, int H, int W, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev,
+                        int n, const unsigned char* masks, size_t mask_bytes, float thr, float border, int* counts, int count_rows,
+                        unsigned char* out_masks, size_t out_bytes, void* stream);
 /* ---- input preprocessing (reference utils/dataset.py:146-168 RefDataset.__getitem__, :207-221 convert; csrc/inputpipe.hip) ----
  * One launch per batch: img_out[b] = ((cv2.warpAffine(rgb_u8, mat, (S_w, S_h), INTER_CUBIC, borderValue=border_rgb).float()
  * / 255 - mean) / std) as [3][S_h][S_w] (through lut_img [3][256]), mask_out[b] = cv2.warpAffine(mask_u8, mat, ...,
