@@ -112,4 +112,9 @@ def _compile(dig, verbose):
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True))
+    if "--print-sources" in sys.argv:       # for shell tools that compile the same list (tools/build_variants.sh)
+        print(" ".join(SOURCES))
+    elif "--print-flags" in sys.argv:
+        print(" ".join(FLAGS))
+    else:
+        print(build(force="--force" in sys.argv, verbose=True))

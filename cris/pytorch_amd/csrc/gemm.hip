@@ -571,7 +571,49 @@ static int skinny_kslice(const cris_conv_gemm_params& p, int slices) { return cr
 
 // tile selection (host)
 enum { V_SKINNY1 = 0, V_SKINNY9, V_SKINNY9S, V_128x64, V_64x64, V_64x128, V_128x128, V_8W_256x256, V_8W_256x128, V_8W_128x256, V_8W_128x128, V_64x64_K2, V_COUNT };
-int cris_launch_gemm8(int variant, const cris_conv_gemm_params& p, int epi, hipStream_t s);       // gemm8.hip
+
+// The variant table, in the order of the enum (tests/test_abi.py pins names and order).  4-wave tiles: 256 threads, a ring of ST
+// stages of (BM + BN) rows of 128 B - at most 72 KB per block, so two blocks (8 waves) share a CU's 160 KB LDS and hide each
+// other's barriers / epilogues.
+#define CRIS_TILE4_KERNS(K, BM, BN, WM, WN, ST) K<BM, BN, WM, WN, ST, 0>, K<BM, BN, WM, WN, ST, 1>, K<BM, BN, WM, WN, ST, 2>
+#define CRIS_TILE4_ROW(NAME, BM, BN, WM, WN, ST)                                                                           \
+    {NAME, BM, BN, 256, ST * (BM + BN) * 128, BM / WM, 8,                                                                  \
+     {CRIS_TILE4_KERNS(conv_gemm_kernel, BM, BN, WM, WN, ST), conv_gemm_kernel<BM, BN, WM, WN, ST, 3>},                  \
+     {CRIS_TILE4_KERNS(conv_gemm_group_kernel, BM, BN, WM, WN, ST)}}
+static const cris_gemm_variant_desc* variant_table() {
+    static const cris_gemm_variant_desc* const g8 = cris_gemm8_variants();
+    static const cris_gemm_variant_desc tab[V_COUNT] = {
+        // skinny kernels (their own launch path): one block = all rows (<= bm) x 32 columns
+        {"skinny1", 16, 32, 64 * SK_WAVES, 0, 16, 8, {}, {}},
+        {"skinny9", SKINNY_MAX_M, 32, 64 * SK_WAVES, 0, 16, 8, {}, {}},
+        {"skinny9s", SKINNY_MAX_M, 32, 64 * SK2_WAVES, 0, 16, 8, {}, {}},
+        CRIS_TILE4_ROW("128x64", 128, 64, 4, 1, ST_128x64),
+        // (measured alternatives for 64x64: 16x16x32 MFMA with four accumulators 19.50 vs 19.39 ms/step, a 2-stage ring with 5
+        // blocks per CU 20.00 ms/step - neither helps)
+        CRIS_TILE4_ROW("64x64", 64, 64, 2, 2, ST_64x64),
+        CRIS_TILE4_ROW("64x128", 64, 128, 2, 2, ST_64x128),
+        CRIS_TILE4_ROW("128x128", 128, 128, 2, 2, ST_128x128),
+        g8[0], g8[1], g8[2], g8[3],
+        // 64x64 with the K-steps split over two wave groups: two-deep ring per group = 64 KB, two blocks (16 waves) per CU
+        {"64x64k2", 64, 64, 512, 2 * 2 * (64 + 64) * 128, 32, 8,
+         {conv_gemm_kernel<64, 64, 2, 2, 2, 0, 32, 2>, conv_gemm_kernel<64, 64, 2, 2, 2, 1, 32, 2>, conv_gemm_kernel<64, 64, 2, 2, 2, 2, 32, 2>, nullptr},
+         {}}};
+    return tab;
+}
+// the dynamic-LDS limit of every kernel of the table, set once
+static int variants_lds_ready() {
+    static const int rc = [] {
+        int rc = 0;
+        for (int v = 0; v < V_COUNT; ++v) {
+            const cris_gemm_variant_desc& r = variant_table()[v];
+            for (int e = 0; e < 4; ++e) rc |= cris_set_lds((const void*)r.kern[e], r.lds_bytes);
+            for (int e = 0; e < 3; ++e) rc |= cris_set_lds((const void*)r.group_kern[e], r.lds_bytes);
+        }
+        return rc;
+    }();
+    if (rc != 0) cris_set_error("gemm variants: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (%d)", rc);
+    return rc;
+}
 
 // which epilogue instantiation a problem takes: 0 general, 1 lean, 2 lean + bias / ReLU (see gemm_epilogue)
 static int epilogue_kind(const cris_conv_gemm_params& p) {
@@ -581,13 +623,11 @@ static int epilogue_kind(const cris_conv_gemm_params& p) {
 }
 
 static bool variant_applicable(int v, const cris_conv_gemm_params& p) {
+    if (v < 0 || v >= V_COUNT) return false;
+    const cris_gemm_variant_desc& r = variant_table()[v];
+    if (r.kern[0]) return p.C % r.c_mult == 0;
     const bool lin = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.OH == p.H && p.OW == p.W;
-    switch (v) {
-        case V_SKINNY1: return lin && p.M <= 16;
-        case V_SKINNY9: case V_SKINNY9S: return lin && p.M <= SKINNY_MAX_M;
-        case V_8W_256x256: case V_8W_256x128: case V_8W_128x256: case V_8W_128x128: return (p.C & 63) == 0;
-        default: return v >= 0 && v < V_COUNT;
-    }
+    return lin && p.M <= r.bm;                  // skinny kernels: a linear problem whose rows fit one block
 }
 
 static int pick_variant(const cris_conv_gemm_params& p) {
@@ -665,17 +705,7 @@ static int pick_variant(const cris_conv_gemm_params& p) {
     return V_128x128;
 }
 // rows per BatchNorm-statistics partial of a variant (= rows of its wave tile)
-static int variant_stat_rows(int v) {
-    switch (v) {
-        case V_SKINNY1: return 16;
-        case V_SKINNY9: return 16;
-        case V_SKINNY9S: return 16;
-        case V_128x128: return 64;
-        case V_8W_256x256: case V_8W_256x128: return 128;
-        case V_8W_128x256: case V_8W_128x128: return 64;
-        default: return 32;
-    }
-}
+static int variant_stat_rows(int v) { return variant_table()[v].stat_rows; }
 static int resolve_variant(const cris_conv_gemm_params& p, int variant) {
     if (variant < 0) return pick_variant(p);
     return variant_applicable(variant, p) ? variant : -1;
@@ -695,27 +725,19 @@ extern "C" int cris_conv_gemm_plan(const cris_conv_gemm_params* p, int variant, 
     return resolve_variant(*p, variant);
 }
 extern "C" int cris_conv_gemm_num_variants(void) { return V_COUNT; }
-extern "C" const char* cris_conv_gemm_variant_name(int v) {
-    static const char* names[V_COUNT] = {"skinny1", "skinny9", "skinny9s", "128x64", "64x64", "64x128", "128x128", "8w256x256", "8w256x128", "8w128x256", "8w128x128", "64x64k2"};
-    return (v >= 0 && v < V_COUNT) ? names[v] : "?";
-}
-
-static int set_lds(const void* kern, int bytes) {
-    return (int)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
+extern "C" const char* cris_conv_gemm_variant_name(int v) { return (v >= 0 && v < V_COUNT) ? variant_table()[v].name : "?"; }
 
 extern "C" int cris_conv_gemm(const cris_conv_gemm_params* pp, void* stream) { return cris_conv_gemm_variant(pp, -1, stream); }
 
 static int conv_gemm_check(const cris_conv_gemm_params& p);
-int cris_launch_gemm8_group(const cris_conv_gemm_group& g, int nblocks, int epi, hipStream_t s);       // gemm8.hip
 
 extern "C" int cris_conv_gemm_group_launch(const cris_conv_gemm_group* gp, int variant, void* stream) {
     CRIS_CHECK_ARG(gp && gp->n > 0 && gp->n <= CRIS_GEMM_GROUP_MAX, "1 .. CRIS_GEMM_GROUP_MAX problems per launch");
-    CRIS_CHECK_ARG(variant == V_128x64 || variant == V_64x64 || variant == V_64x128 || variant == V_128x128 || variant == V_8W_128x128,
+    CRIS_CHECK_ARG(variant >= 0 && variant < V_COUNT && variant_table()[variant].group_kern[0],
                    "group launches run the 4-wave tiles or the 8-wave 128x128 tile");
     if (gp->n == 1) return cris_conv_gemm_variant(&gp->prob[0], variant, stream);
+    const cris_gemm_variant_desc& r = variant_table()[variant];
     cris_conv_gemm_group g = *gp;
-    static const int bm[V_COUNT] = {0, 0, 0, 128, 64, 64, 128, 256, 256, 128, 128, 64}, bn[V_COUNT] = {0, 0, 0, 64, 64, 128, 128, 256, 128, 256, 128, 64};
     const int epi = epilogue_kind(g.prob[0]);
     CRIS_CHECK_ARG(epi < 3, "BatchNorm-backward partials are not available in grouped launches");
     int start = 0;
@@ -725,41 +747,11 @@ extern "C" int cris_conv_gemm_group_launch(const cris_conv_gemm_group* gp, int v
         CRIS_CHECK_ARG(epilogue_kind(p) == epi, "the problems of a group must share the epilogue instantiation");
         CRIS_CHECK_ARG(variant_applicable(variant, p), "tile variant not applicable to a problem of the group");
         g.block_start[i] = start;
-        start += cris_cdiv(p.M, bm[variant]) * cris_cdiv(p.N, bn[variant]);
+        start += cris_tile_blocks(r.bm, r.bn, p.M, p.N);
     }
     for (int i = g.n; i <= CRIS_GEMM_GROUP_MAX; ++i) g.block_start[i] = start;
-    hipStream_t s = (hipStream_t)stream;
-    if (variant == V_8W_128x128) return cris_launch_gemm8_group(g, start, epi, s);
-    constexpr int LDS_128x64 = ST_128x64 * (128 + 64) * 128, LDS_64x128 = ST_64x128 * (64 + 128) * 128;
-    constexpr int LDS_128x128 = ST_128x128 * (128 + 128) * 128, LDS_64x64 = ST_64x64 * (64 + 64) * 128;
-    typedef void (*kern_t)(const cris_conv_gemm_group);
-    static const kern_t k_128x64[3] = {conv_gemm_group_kernel<128, 64, 4, 1, ST_128x64, 0>, conv_gemm_group_kernel<128, 64, 4, 1, ST_128x64, 1>,
-                                       conv_gemm_group_kernel<128, 64, 4, 1, ST_128x64, 2>};
-    static const kern_t k_64x128[3] = {conv_gemm_group_kernel<64, 128, 2, 2, ST_64x128, 0>, conv_gemm_group_kernel<64, 128, 2, 2, ST_64x128, 1>,
-                                       conv_gemm_group_kernel<64, 128, 2, 2, ST_64x128, 2>};
-    static const kern_t k_128x128[3] = {conv_gemm_group_kernel<128, 128, 2, 2, ST_128x128, 0>, conv_gemm_group_kernel<128, 128, 2, 2, ST_128x128, 1>,
-                                        conv_gemm_group_kernel<128, 128, 2, 2, ST_128x128, 2>};
-    static const kern_t k_64x64[3] = {conv_gemm_group_kernel<64, 64, 2, 2, ST_64x64, 0>, conv_gemm_group_kernel<64, 64, 2, 2, ST_64x64, 1>,
-                                      conv_gemm_group_kernel<64, 64, 2, 2, ST_64x64, 2>};
-    static const int lds_ready = [&]() {
-        int rc = 0;
-        for (int e = 0; e < 3; ++e)
-            rc |= set_lds((const void*)k_128x64[e], LDS_128x64) | set_lds((const void*)k_64x128[e], LDS_64x128) |
-                  set_lds((const void*)k_128x128[e], LDS_128x128) | set_lds((const void*)k_64x64[e], LDS_64x64);
-        return rc;
-    }();
-    if (lds_ready != 0) {
-        cris_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (%d)", __func__, lds_ready);
-        return lds_ready;
-    }
-    switch (variant) {
-        case V_128x64: hipLaunchKernelGGL(k_128x64[epi], dim3(start), dim3(256), LDS_128x64, s, g); break;
-        case V_64x64: hipLaunchKernelGGL(k_64x64[epi], dim3(start), dim3(256), LDS_64x64, s, g); break;
-        case V_64x128: hipLaunchKernelGGL(k_64x128[epi], dim3(start), dim3(256), LDS_64x128, s, g); break;
-        default: hipLaunchKernelGGL(k_128x128[epi], dim3(start), dim3(256), LDS_128x128, s, g);
-    }
-    CRIS_LAUNCH_CHECK();
-    return 0;
+    if (const int rc = variants_lds_ready()) return rc;
+    return cris_launch_tile(r.group_kern[epi], start, r.threads, r.lds_bytes, (hipStream_t)stream, g);
 }
 
 static int conv_gemm_check(const cris_conv_gemm_params& p) {
@@ -790,79 +782,29 @@ extern "C" int cris_conv_gemm_variant(const cris_conv_gemm_params* pp, int varia
     const cris_conv_gemm_params& p = *pp;
     if (conv_gemm_check(p) != 0) return -1;
     hipStream_t s = (hipStream_t)stream;
-    // <= 72 KB per block: two blocks (8 waves) share a CU's 160 KB LDS and hide each other's barriers / epilogues
-    constexpr int LDS_128x64 = ST_128x64 * (128 + 64) * 128, LDS_64x128 = ST_64x128 * (64 + 128) * 128;
-    constexpr int LDS_128x128 = ST_128x128 * (128 + 128) * 128, LDS_64x64 = ST_64x64 * (64 + 64) * 128;
-    typedef void (*kern_t)(const cris_conv_gemm_params);
-    // [variant][epilogue: 0 general, 1 lean, 2 lean + bias / ReLU]
-    static const kern_t k_128x64[4] = {conv_gemm_kernel<128, 64, 4, 1, ST_128x64, 0>, conv_gemm_kernel<128, 64, 4, 1, ST_128x64, 1>,
-                                       conv_gemm_kernel<128, 64, 4, 1, ST_128x64, 2>, conv_gemm_kernel<128, 64, 4, 1, ST_128x64, 3>};
-    static const kern_t k_64x128[4] = {conv_gemm_kernel<64, 128, 2, 2, ST_64x128, 0>, conv_gemm_kernel<64, 128, 2, 2, ST_64x128, 1>,
-                                       conv_gemm_kernel<64, 128, 2, 2, ST_64x128, 2>, conv_gemm_kernel<64, 128, 2, 2, ST_64x128, 3>};
-    static const kern_t k_128x128[4] = {conv_gemm_kernel<128, 128, 2, 2, ST_128x128, 0>, conv_gemm_kernel<128, 128, 2, 2, ST_128x128, 1>,
-                                        conv_gemm_kernel<128, 128, 2, 2, ST_128x128, 2>, conv_gemm_kernel<128, 128, 2, 2, ST_128x128, 3>};
-    // (measured alternatives for this variant: 16x16x32 MFMA with four accumulators 19.50 vs 19.39 ms/step, a 2-stage ring
-    // with 5 blocks per CU 20.00 ms/step - neither helps)
-    static const kern_t k_64x64[4] = {conv_gemm_kernel<64, 64, 2, 2, ST_64x64, 0>, conv_gemm_kernel<64, 64, 2, 2, ST_64x64, 1>,
-                                      conv_gemm_kernel<64, 64, 2, 2, ST_64x64, 2>, conv_gemm_kernel<64, 64, 2, 2, ST_64x64, 3>};
-    // 64x64 with the K-steps split over two wave groups: two-deep ring per group = 64 KB, two blocks (16 waves) per CU
-    constexpr int ST_K2 = 2, LDS_64x64K2 = 2 * ST_K2 * (64 + 64) * 128;
-    static const kern_t k_64x64k2[3] = {conv_gemm_kernel<64, 64, 2, 2, ST_K2, 0, 32, 2>, conv_gemm_kernel<64, 64, 2, 2, ST_K2, 1, 32, 2>,
-                                        conv_gemm_kernel<64, 64, 2, 2, ST_K2, 2, 32, 2>};
-    static const int lds_ready = [&]() {
-        int rc = 0;
-        for (int e = 0; e < 3; ++e) rc |= set_lds((const void*)k_64x64k2[e], LDS_64x64K2);
-        for (int e = 0; e < 4; ++e)
-            rc |= set_lds((const void*)k_128x64[e], LDS_128x64) | set_lds((const void*)k_64x128[e], LDS_64x128) |
-                  set_lds((const void*)k_128x128[e], LDS_128x128) | set_lds((const void*)k_64x64[e], LDS_64x64);
-        return rc;
-    }();
-    if (lds_ready != 0) {
-        cris_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (%d)", __func__, lds_ready);
-        return lds_ready;
-    }
-    const int lean = epilogue_kind(p);
+    if (const int rc = variants_lds_ready()) return rc;
     int v = resolve_variant(p, variant);
     CRIS_CHECK_ARG(v >= 0, "tile variant not applicable to this problem");
     // automatic choice without a workspace (a caller that predates the `ws` field): the single-pass skinny kernel (same rows
     // per statistics partial as the split-K one) instead of an error
     if (variant < 0 && v == V_SKINNY9S && !p.ws) v = V_SKINNY9;
-    CRIS_CHECK_ARG(!p.bnr_y || v == V_128x64 || v == V_64x64 || v == V_64x128 || v == V_128x128 || v == V_8W_128x128,
+    const cris_gemm_variant_desc& r = variant_table()[v];
+    CRIS_CHECK_ARG(!p.bnr_y || r.kern[3],
                    "BatchNorm-backward partials: the 4-wave tiles and the 8-wave 128x128 tile only (cris_conv_gemm_plan tells which variant runs)");
+    const int nblocks = cris_cdiv(p.N, r.bn);               // (skinny kernels: one block per 32 columns)
     switch (v) {
-        case V_8W_256x256: case V_8W_256x128: case V_8W_128x256: case V_8W_128x128:
-            return cris_launch_gemm8(v - V_8W_256x256, p, lean, s);
-        case V_SKINNY1:
-            hipLaunchKernelGGL(skinny_gemm_kernel<1>, dim3(cris_cdiv(p.N, 32)), dim3(64 * SK_WAVES), 0, s, p);
-            break;
+        case V_SKINNY1: return cris_launch_tile(skinny_gemm_kernel<1>, nblocks, r.threads, 0, s, p);
+        case V_SKINNY9: return cris_launch_tile(skinny_gemm_kernel<9>, nblocks, r.threads, 0, s, p);
         case V_SKINNY9S: {
             CRIS_CHECK_ARG(p.ws != nullptr, "the split-K skinny variant needs the workspace (cris_conv_gemm_ws_floats)");
-            const int slices = skinny_split_slices(p), nblocks = cris_cdiv(p.N, 32);
-            hipLaunchKernelGGL(skinny_split_kernel<9>, dim3(nblocks, slices), dim3(64 * SK2_WAVES), 0, s, p, skinny_kslice(p, slices));
+            const int slices = skinny_split_slices(p);
+            hipLaunchKernelGGL(skinny_split_kernel<9>, dim3(nblocks, slices), dim3(r.threads), 0, s, p, skinny_kslice(p, slices));
             hipLaunchKernelGGL(skinny_finish_kernel<9>, dim3(cris_cdiv(9 * nblocks * 2, 4)), dim3(256), 0, s, p, slices, nblocks);
-            break;
+            CRIS_LAUNCH_CHECK();
+            return 0;
         }
-        case V_SKINNY9:
-            hipLaunchKernelGGL(skinny_gemm_kernel<9>, dim3(cris_cdiv(p.N, 32)), dim3(64 * SK_WAVES), 0, s, p);
-            break;
-        case V_128x64:
-            hipLaunchKernelGGL(k_128x64[lean], dim3(cris_cdiv(p.M, 128) * cris_cdiv(p.N, 64)), dim3(256), LDS_128x64, s, p);
-            break;
-        case V_64x64:
-            hipLaunchKernelGGL(k_64x64[lean], dim3(cris_cdiv(p.M, 64) * cris_cdiv(p.N, 64)), dim3(256), LDS_64x64, s, p);
-            break;
-        case V_64x64_K2:
-            CRIS_CHECK_ARG(lean < 3, "the K-split 64x64 tile has no BatchNorm-backward epilogue");
-            hipLaunchKernelGGL(k_64x64k2[lean], dim3(cris_cdiv(p.M, 64) * cris_cdiv(p.N, 64)), dim3(512), LDS_64x64K2, s, p);
-            break;
-        case V_64x128:
-            hipLaunchKernelGGL(k_64x128[lean], dim3(cris_cdiv(p.M, 64) * cris_cdiv(p.N, 128)), dim3(256), LDS_64x128, s, p);
-            break;
-        default:
-            hipLaunchKernelGGL(k_128x128[lean], dim3(cris_cdiv(p.M, 128) * cris_cdiv(p.N, 128)), dim3(256), LDS_128x128, s, p);
+        default: return cris_launch_tile(r.kern[epilogue_kind(p)], cris_tile_blocks(r.bm, r.bn, p.M, p.N), r.threads, r.lds_bytes, s, p);
     }
-    CRIS_LAUNCH_CHECK();
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -61,6 +61,8 @@
 //   (160 KB): the variant for problems of at most ~one tile per CU (mid-size layers), whose loop is bound by the operand
 //   latency - three K-tiles (96 KB) stay in flight per CU against one or two with the 4-wave tiles' rings
 // `bid`: the tile of the problem this block computes, in the XCD-aware order of the launch
+constexpr int gemm8_nbuf(int PA, int PB) { return (PA == 2 && PB == 2) ? 2 : (PA == 1 && PB == 1) ? 5 : 3; }      // K-tile buffers
+
 template <int PA, int PB, int EPI>
 __device__ __forceinline__ void conv_gemm8_tile(const cris_conv_gemm_params& p, int bid, unsigned char* smem) {
     constexpr int WTM = PA * 64, WTN = PB * 32;
@@ -68,7 +70,7 @@ __device__ __forceinline__ void conv_gemm8_tile(const cris_conv_gemm_params& p, 
     constexpr int FM = PA * 2, FN = PB;
     constexpr bool S4 = PA == 2 && PB == 2;
     constexpr bool S1 = PA == 1 && PB == 1;
-    constexpr int NBUF = S4 ? 2 : S1 ? 5 : 3;
+    constexpr int NBUF = gemm8_nbuf(PA, PB);
     constexpr bool DMA_IN_MFMA = (!S4) != ((G8_ABL & 128) != 0);      // where a phase issues its LDS-DMAs (see G8_ABL bit 7)
     constexpr int A_BYTES = BM * 128, TILE_BYTES = (BM + BN) * 128;
 
@@ -394,57 +396,15 @@ __global__ __launch_bounds__(512) void conv_gemm8_group_kernel(const cris_conv_g
     conv_gemm8_tile<1, 1, EPI>(p, lb - g.block_start[pi], smem);
 }
 
-static int set_lds8(const void* kern, int bytes) {
-    return (int)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
-// launcher used by cris_conv_gemm (gemm.hip): variant 0 = 256x256, 1 = 256x128, 2 = 128x256, 3 = 128x128; epi as in gemm.hip
-int cris_launch_gemm8(int variant, const cris_conv_gemm_params& p, int epi, hipStream_t s) {
-    typedef void (*kern_t)(const cris_conv_gemm_params);
-    if (epi == 3) {                               // lean + BatchNorm-backward partials: the 128x128 tile only
-        static const kern_t k3 = conv_gemm8_kernel<1, 1, 3>;
-        static const int ready3 = set_lds8((const void*)k3, 5 * (128 + 128) * 128);
-        CRIS_CHECK_ARG(ready3 == 0, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-        CRIS_CHECK_ARG(variant == 3 && (p.C & 63) == 0, "BatchNorm-backward partials: 8-wave 128x128 tile only, C % 64 == 0");
-        hipLaunchKernelGGL(k3, dim3(cris_cdiv(p.M, 128) * cris_cdiv(p.N, 128)), dim3(512), 5 * (128 + 128) * 128, s, p);
-        CRIS_LAUNCH_CHECK();
-        return 0;
-    }
-    static const kern_t k[4][3] = {
-        {conv_gemm8_kernel<2, 2, 0>, conv_gemm8_kernel<2, 2, 1>, conv_gemm8_kernel<2, 2, 2>},
-        {conv_gemm8_kernel<2, 1, 0>, conv_gemm8_kernel<2, 1, 1>, conv_gemm8_kernel<2, 1, 2>},
-        {conv_gemm8_kernel<1, 2, 0>, conv_gemm8_kernel<1, 2, 1>, conv_gemm8_kernel<1, 2, 2>},
-        {conv_gemm8_kernel<1, 1, 0>, conv_gemm8_kernel<1, 1, 1>, conv_gemm8_kernel<1, 1, 2>}};
-    static const int lds[4] = {2 * (256 + 256) * 128, 3 * (256 + 128) * 128, 3 * (128 + 256) * 128, 5 * (128 + 128) * 128};
-    static const int bm[4] = {256, 256, 128, 128}, bn[4] = {256, 128, 256, 128};
-    static const int ready = [&]() {
-        int rc = 0;
-        for (int v = 0; v < 4; ++v)
-            for (int e = 0; e < 3; ++e) rc |= set_lds8((const void*)k[v][e], lds[v]);
-        return rc;
-    }();
-    if (ready != 0) {
-        cris_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (%d)", __func__, ready);
-        return ready;
-    }
-    CRIS_CHECK_ARG(variant >= 0 && variant < 4, "unknown 8-wave variant");
-    CRIS_CHECK_ARG((p.C & 63) == 0, "8-wave tiles need C % 64 == 0");
-    hipLaunchKernelGGL(k[variant][epi], dim3(cris_cdiv(p.M, bm[variant]) * cris_cdiv(p.N, bn[variant])), dim3(512), lds[variant], s, p);
-    CRIS_LAUNCH_CHECK();
-    return 0;
-}
-
-int cris_launch_gemm8_group(const cris_conv_gemm_group& g, int nblocks, int epi, hipStream_t s) {
-    typedef void (*kern_t)(const cris_conv_gemm_group);
-    static const kern_t k[3] = {conv_gemm8_group_kernel<0>, conv_gemm8_group_kernel<1>, conv_gemm8_group_kernel<2>};
-    constexpr int LDS = 5 * (128 + 128) * 128;
-    static const int ready = set_lds8((const void*)k[0], LDS) | set_lds8((const void*)k[1], LDS) | set_lds8((const void*)k[2], LDS);
-    if (ready != 0) {
-        cris_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (%d)", __func__, ready);
-        return ready;
-    }
-    for (int i = 0; i < g.n; ++i) CRIS_CHECK_ARG((g.prob[i].C & 63) == 0, "8-wave tiles need C % 64 == 0");
-    hipLaunchKernelGGL(k[epi], dim3(nblocks), dim3(512), LDS, s, g);
-    CRIS_LAUNCH_CHECK();
-    return 0;
+// The four rows of the variant table (gemm.hip: variant_table) in the order 256x256, 256x128, 128x256, 128x128: block tile
+// PA*128 x PB*128, 512 threads, gemm8_nbuf K-tile buffers of (BM + BN) rows of 128 B, wave tile rows PA*64; all need C % 64 == 0.
+// Only the 128x128 tile has the BatchNorm-backward epilogue and a group kernel.
+#define CRIS_TILE8_ROW(NAME, PA, PB, K3, ...)                                                               \
+    {NAME, PA * 128, PB * 128, 512, gemm8_nbuf(PA, PB) * (PA * 128 + PB * 128) * 128, PA * 64, 64,           \
+     {conv_gemm8_kernel<PA, PB, 0>, conv_gemm8_kernel<PA, PB, 1>, conv_gemm8_kernel<PA, PB, 2>, K3}, {__VA_ARGS__}}
+const cris_gemm_variant_desc* cris_gemm8_variants() {
+    static const cris_gemm_variant_desc rows[4] = {
+        CRIS_TILE8_ROW("8w256x256", 2, 2, nullptr), CRIS_TILE8_ROW("8w256x128", 2, 1, nullptr), CRIS_TILE8_ROW("8w128x256", 1, 2, nullptr),
+        CRIS_TILE8_ROW("8w128x128", 1, 1, (conv_gemm8_kernel<1, 1, 3>), conv_gemm8_group_kernel<0>, conv_gemm8_group_kernel<1>, conv_gemm8_group_kernel<2>)};
+    return rows;
 }

@@ -1,5 +1,7 @@
-// Pieces shared by the implicit-GEMM kernels (gemm.hip: 4-wave tiles, skinny kernel; gemm8.hip: 8-wave ping-pong tiles):
-// the XOR-swizzled LDS row layout and the epilogue of one wave tile.
+// Pieces shared by the implicit-GEMM kernels (gemm.hip: 4-wave tiles, skinny kernels; gemm8.hip: 8-wave ping-pong tiles;
+// gemm_fp8.hip: the fp8 inference tiles).  Device: the XCD-aware block order, the XOR-swizzled LDS row layout and the epilogue of
+// one wave tile.  Host (end of the file): the descriptor of one tile variant - each file defines its rows next to its
+// instantiations, gemm.hip assembles the table - and the grid / dynamic-LDS / launch routines every launch path uses.
 #pragma once
 #include "common.h"
 #include "../../../include/cris_hip.h"
@@ -434,3 +436,32 @@ __device__ __forceinline__ void gemm_epilogue(const cris_conv_gemm_params& p, AC
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// tile variants (host): every fact of one variant is written once, in its row, next to the instantiations the row names
+// ------------------------------------------------------------------------------------------------
+typedef void (*cris_gemm_kern_t)(const cris_conv_gemm_params);
+typedef void (*cris_gemm_group_kern_t)(const cris_conv_gemm_group);
+struct cris_gemm_variant_desc {
+    const char* name;
+    int bm, bn;                         // block tile (skinny kernels: the rows one block takes x its 32 columns)
+    int threads, lds_bytes;             // launch geometry; lds_bytes = dynamic LDS
+    int stat_rows;                      // rows per BatchNorm-statistics partial (= rows of the wave tile)
+    int c_mult;                         // the tile needs C % c_mult == 0
+    cris_gemm_kern_t kern[4];           // per epilogue kind (0 general, 1 lean, 2 lean + bias / ReLU, 3 lean + BatchNorm-backward
+                                        // partials); null = not instantiated.  All null: a launch path of its own (skinny)
+    cris_gemm_group_kern_t group_kern[3];       // several problems per launch; null = not groupable
+};
+const cris_gemm_variant_desc* cris_gemm8_variants();      // gemm8.hip: its four rows (256x256, 256x128, 128x256, 128x128)
+
+static inline int cris_tile_blocks(int bm, int bn, int M, int N) { return cris_cdiv(M, bm) * cris_cdiv(N, bn); }
+static inline int cris_set_lds(const void* kern, int bytes) {
+    return kern ? (int)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) : 0;
+}
+// launch one tile kernel (single problem, group or fp8: ARG is what the kernel takes)
+template <typename KERN, typename ARG>
+static int cris_launch_tile(KERN kern, int blocks, int threads, int lds_bytes, hipStream_t s, const ARG& arg) {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds_bytes, s, arg);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}

@@ -44,6 +44,24 @@ __device__ __forceinline__ int cris_e4m3_exponent(float amax) {
     return m <= 0.875f ? q - 9 : q - 8;
 }
 
+// 256-thread block maximum through LDS in a fixed tree order (no atomics); every thread returns the result
+__device__ __forceinline__ float block_max_256(float* red, float v) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// the 32 operand bytes of one lane for K slice ks (0 / 1) of a 128-B LDS row: 16-B chunks ks*4 + fh*2 and the next one
+__device__ __forceinline__ i32x8 fp8_fragment(const unsigned char* base, int row, int ks, int fh) {
+    const u32x4 lo = *reinterpret_cast<const u32x4*>(base + lds_off(row, ks * 4 + fh * 2));
+    const u32x4 hi = *reinterpret_cast<const u32x4*>(base + lds_off(row, ks * 4 + fh * 2 + 1));
+    return (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+}
+
 // ------------------------------------------------------------------------------------------------
 // the convolution
 // ------------------------------------------------------------------------------------------------
@@ -207,19 +225,9 @@ __global__ __launch_bounds__(256) void conv_gemm_fp8_kernel(const cris_conv_gemm
         for (int ks = 0; ks < 2; ++ks) {
             i32x8 af[FM], bfr[FN];
 #pragma unroll
-            for (int i = 0; i < FM; ++i) {
-                const int row = wm * WTM + i * 32 + fr;
-                const u32x4 lo = *reinterpret_cast<const u32x4*>(sa + lds_off(row, ks * 4 + fh * 2));
-                const u32x4 hi = *reinterpret_cast<const u32x4*>(sa + lds_off(row, ks * 4 + fh * 2 + 1));
-                af[i] = (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-            }
+            for (int i = 0; i < FM; ++i) af[i] = fp8_fragment(sa, wm * WTM + i * 32 + fr, ks, fh);
 #pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                const int row = wn * WTN + j * 32 + fr;
-                const u32x4 lo = *reinterpret_cast<const u32x4*>(sb + lds_off(row, ks * 4 + fh * 2));
-                const u32x4 hi = *reinterpret_cast<const u32x4*>(sb + lds_off(row, ks * 4 + fh * 2 + 1));
-                bfr[j] = (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-            }
+            for (int j = 0; j < FN; ++j) bfr[j] = fp8_fragment(sb, wn * WTN + j * 32 + fr, ks, fh);
 #pragma unroll
             for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -278,6 +286,14 @@ __global__ __launch_bounds__(256) void conv_gemm_fp8_kernel(const cris_conv_gemm
 }
 
 enum { V8_128x128 = 0, V8_64x64 = 1, V8_COUNT = 2 };
+// the two tile variants, in the order of the enum: 256 threads, a ring of ST stages of (BM + BN) rows of 128 B
+struct fp8_variant_desc {
+    const char* name;
+    int bm, bn, threads, lds_bytes;
+    void (*kern)(const cris_conv_gemm_fp8_params);
+};
+#define CRIS_FP8_ROW(NAME, BM, BN, ST) {NAME, BM, BN, 256, ST * (BM + BN) * 128, conv_gemm_fp8_kernel<BM, BN, 2, 2, ST>}
+static const fp8_variant_desc fp8_variants[V8_COUNT] = {CRIS_FP8_ROW("128x128", 128, 128, ST8_128x128), CRIS_FP8_ROW("64x64", 64, 64, ST8_64x64)};
 
 static int fp8_pick_variant(const cris_conv_gemm_fp8_params& p) {
     // as the bf16 plan: narrow problems and grids of too few 128x128 tiles to fill the chip take the 64x64 tile
@@ -312,32 +328,24 @@ extern "C" int cris_conv_gemm_fp8_plan(const cris_conv_gemm_fp8_params* p, int v
     return variant < V8_COUNT ? variant : -1;
 }
 extern "C" int cris_conv_gemm_fp8_num_variants(void) { return V8_COUNT; }
-extern "C" const char* cris_conv_gemm_fp8_variant_name(int v) {
-    static const char* names[V8_COUNT] = {"128x128", "64x64"};
-    return (v >= 0 && v < V8_COUNT) ? names[v] : "?";
-}
+extern "C" const char* cris_conv_gemm_fp8_variant_name(int v) { return (v >= 0 && v < V8_COUNT) ? fp8_variants[v].name : "?"; }
 
 extern "C" int cris_conv_gemm_fp8(const cris_conv_gemm_fp8_params* pp, int variant, void* stream) {
     const cris_conv_gemm_fp8_params& p = *pp;
     if (conv_gemm_fp8_check(p) != 0) return -1;
     const int v = cris_conv_gemm_fp8_plan(pp, variant);
     CRIS_CHECK_ARG(v >= 0, "fp8 tile variant out of range");
-    constexpr int LDS_128 = ST8_128x128 * (128 + 128) * 128, LDS_64 = ST8_64x64 * (64 + 64) * 128;
-    static const int lds_ready = (int)hipFuncSetAttribute((const void*)conv_gemm_fp8_kernel<128, 128, 2, 2, ST8_128x128>,
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS_128) |
-                                 (int)hipFuncSetAttribute((const void*)conv_gemm_fp8_kernel<64, 64, 2, 2, ST8_64x64>,
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS_64);
+    static const int lds_ready = [] {
+        int rc = 0;
+        for (const fp8_variant_desc& r : fp8_variants) rc |= cris_set_lds((const void*)r.kern, r.lds_bytes);
+        return rc;
+    }();
     if (lds_ready != 0) {
         cris_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (%d)", __func__, lds_ready);
         return lds_ready;
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (v == V8_128x128)
-        hipLaunchKernelGGL((conv_gemm_fp8_kernel<128, 128, 2, 2, ST8_128x128>), dim3(cris_cdiv(p.M, 128) * cris_cdiv(p.N, 128)), dim3(256), LDS_128, s, p);
-    else
-        hipLaunchKernelGGL((conv_gemm_fp8_kernel<64, 64, 2, 2, ST8_64x64>), dim3(cris_cdiv(p.M, 64) * cris_cdiv(p.N, 64)), dim3(256), LDS_64, s, p);
-    CRIS_LAUNCH_CHECK();
-    return 0;
+    const fp8_variant_desc& r = fp8_variants[v];
+    return cris_launch_tile(r.kern, cris_tile_blocks(r.bm, r.bn, p.M, p.N), r.threads, r.lds_bytes, (hipStream_t)stream, p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -360,13 +368,7 @@ __global__ __launch_bounds__(256) void pack_weights_fp8_kernel(const cris_pack_f
     const float* src = d.src + (size_t)n * d.Cin * d.taps;          // parameter layout [N][Cin][taps]
     float amax = 0.f;
     for (int i = threadIdx.x; i < d.Cin * d.taps; i += 256) amax = fmaxf(amax, fabsf(src[i] * rs));
-    red[threadIdx.x] = amax;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    const int e = cris_e4m3_exponent(red[0]);
+    const int e = cris_e4m3_exponent(block_max_256(red, amax));
     if (threadIdx.x == 0) d.e_w[n] = e;
     uint8_t* dst = d.dst + (size_t)n * d.ld;
     for (int i = threadIdx.x; i < d.ld; i += 256) {
@@ -451,26 +453,16 @@ __global__ __launch_bounds__(256) void absmax_partial_kernel(const bf16_t* __res
 #pragma unroll
         for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(t[j]));
     }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+    m = block_max_256(red, m);
+    if (threadIdx.x == 0) part[blockIdx.x] = m;
 }
 
 __global__ __launch_bounds__(256) void absmax_final_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
     __shared__ float red[256];
     float m = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, part[i]);
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0];
+    m = block_max_256(red, m);
+    if (threadIdx.x == 0) out[0] = m;
 }
 
 extern "C" int cris_absmax_ws_floats(void) { return ABSMAX_BLOCKS; }

@@ -5,8 +5,9 @@
 set -e
 cd "$(dirname "$0")/../cris/pytorch_amd/csrc"
 mkdir -p variants
-SRC="api.hip gemm.hip gemm8.hip wgrad.hip norm.hip attention.hip elementwise.hip smallf32.hip evalpost.hip inputpipe.hip p2p.hip comm.hip jpeg.hip png.hip"
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -fno-slp-vectorize -fno-vectorize"
+# source list and flags are build.py's, so that an A/B build cannot go stale against the library
+SRC="$(python build.py --print-sources)"
+FLAGS="$(python build.py --print-flags)"
 for spec in "$@"; do
   tag="${spec%%:*}"; extra="${spec#*:}"
   d=variants/obj_$tag; mkdir -p $d

@@ -16,8 +16,10 @@ void cris_set_error(const char* fmt, ...) {
     va_end(ap);
     fputc('\n', stderr);
 }
-int cris_launch_gemm8(int, const cris_conv_gemm_params&, int, hipStream_t) { return -1; }                 // (gemm8.hip is not linked)
-int cris_launch_gemm8_group(const cris_conv_gemm_group&, int, int, hipStream_t) { return -1; }
+const cris_gemm_variant_desc* cris_gemm8_variants() {                 // (gemm8.hip is not linked: names only, no kernels)
+    static const cris_gemm_variant_desc none[4] = {{"8w256x256", 256, 256}, {"8w256x128", 256, 128}, {"8w128x256", 128, 256}, {"8w128x128", 128, 128}};
+    return none;
+}
 
 static unsigned short f2bf_host(float f) {
     unsigned u;
@@ -72,8 +74,8 @@ int main(int argc, char** argv) {
         hipMemcpy(dA, ha.data(), na * 2, hipMemcpyHostToDevice);
     }
 #endif
-    static const int bm[V_COUNT] = {0, 0, 0, 128, 64, 64, 128, 256, 256, 128, 128, 64}, bn[V_COUNT] = {0, 0, 0, 64, 64, 128, 128, 256, 128, 256, 128, 64};
-    const int blocks = cris_cdiv(p.M, bm[variant]) * cris_cdiv(p.N, bn[variant]);
+    if (!variant_table()[variant].kern[1] || variant_table()[variant].threads != 256) { fprintf(stderr, "not a 4-wave tile: %s\n", argv[1]); return 2; }
+    const int blocks = cris_tile_blocks(variant_table()[variant].bm, variant_table()[variant].bn, p.M, p.N);
     unsigned long long* dst = nullptr;
     hipMalloc((void**)&dst, (size_t)blocks * 8 * 8);
     hipMemset(dst, 0, (size_t)blocks * 8 * 8);

@@ -41,7 +41,13 @@ int main(int argc, char** argv) {
     void *dA, *dW, *dO;
     float *cs, *cq;
     hipMalloc(&dA, na * 2); hipMalloc(&dW, nw * 2); hipMalloc(&dO, no * 2);
-    const int rows = variant >= 2 ? 64 : 128;
+    hipStream_t st;
+    hipStreamCreate(&st);
+    if (variant < 0 || variant > 3) { fprintf(stderr, "variant 0 .. 3\n"); return 2; }
+    const cris_gemm_variant_desc& row = cris_gemm8_variants()[variant];
+    const int rows = row.stat_rows;
+    if (cris_set_lds((const void*)row.kern[1], row.lds_bytes) != 0) return 1;
+    auto launch = [&]() { return cris_launch_tile(row.kern[1], cris_tile_blocks(row.bm, row.bn, p.M, p.N), row.threads, row.lds_bytes, st, p); };
     const size_t nst = (size_t)((p.M + rows - 1) / rows) * N;
     hipMalloc((void**)&cs, nst * 4); hipMalloc((void**)&cq, nst * 4);
     hipMemcpy(dA, ha.data(), na * 2, hipMemcpyHostToDevice);
@@ -49,17 +55,15 @@ int main(int argc, char** argv) {
     p.A = (const cris_bf16*)dA; p.Wt = (const cris_bf16*)dW; p.out = dO; p.colsum = cs; p.colsq = cq;
     if (mode == 1) p.out = nullptr;
     if (mode == 2) p.colsum = p.colsq = nullptr;
-    hipStream_t st;
-    hipStreamCreate(&st);
     for (int i = 0; i < 3; ++i)
-        if (cris_launch_gemm8(variant, p, 1, st) != 0) return 1;
+        if (launch() != 0) return 1;
     hipStreamSynchronize(st);
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     float best = 1e30f, tot = 0.f;
     for (int r = 0; r < 5; ++r) {
         hipEventRecord(e0, st);
-        for (int i = 0; i < reps; ++i) cris_launch_gemm8(variant, p, 1, st);
+        for (int i = 0; i < reps; ++i) launch();
         hipEventRecord(e1, st);
         hipEventSynchronize(e1);
         float ms;
