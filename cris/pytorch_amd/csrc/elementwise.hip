@@ -1048,6 +1048,107 @@ extern "C" int cris_adam_step(const cris_adam_desc* dev_table, int n_desc, int t
                               nullptr, nullptr, pack_taps, stream);
 }
 
+// ------------------------------------------------------------------------------------------------
+// global gradient norm (torch.nn.utils.clip_grad_norm_, engine/engine.py:54-55) over an Adam table
+// ------------------------------------------------------------------------------------------------
+// Block b of the table's partition (the one adam_kernel runs: block_start / cris_adam_blocks) writes partials[b] = the sum of
+// g^2 over the elements that block updates, g read where the update reads it.  Only logical elements are visited, so the
+// padding columns cin <= c < cpad of a GEMM-layout gradient never enter the sum.  Fixed order: a thread adds its elements in
+// index order, the wave reduces by the xor butterfly of wave_sum, wave 0 adds the four wave sums in wave order - no atomics,
+// the same bits on every run.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const cris_adam_desc* __restrict__ tab, int n_desc, float* __restrict__ partials) {
+    int lo = 0, hi = n_desc - 1;
+    const int bid = blockIdx.x;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].block_start <= bid) lo = mid; else hi = mid - 1;
+    }
+    const cris_adam_desc d = tab[lo];
+    const int lb = bid - d.block_start;
+    float acc = 0.f;
+    if (d.dstF || d.dstD) {               // a tile of a packed weight (adam_pack_tile): TN rows x 64 channels x all taps
+        const int PT = d.taps == 9 ? 9 : 1, TN = d.taps == 9 ? AP_TN(9) : AP_TN(1);
+        const int tiles_c = (d.cin + AP_T - 1) / AP_T;
+        const int tn = lb / tiles_c, tc = lb - tn * tiles_c;
+        const int n0 = tn * TN, c0 = tc * AP_T;
+        const int rows = min(TN, d.N - n0), cw = min(AP_T, d.cin - c0);
+        if (d.transposed) {               // gradient [c][n] like the parameter: consecutive threads = consecutive rows n
+            for (int i = threadIdx.x; i < cw * AP_T; i += 256) {
+                const int c_l = i / AP_T, n_l = i - c_l * AP_T;
+                if (n_l >= rows) continue;
+                const float g = d.g[(long)(c0 + c_l) * d.N + n0 + n_l];
+                acc += g * g;
+            }
+        } else {                          // [n][tap][cpad] (taps > 0) or [n][c] (one tap): consecutive threads = consecutive channels
+            for (int i = threadIdx.x; i < rows * PT * AP_T; i += 256) {
+                const int c_l = i & (AP_T - 1), r = i >> 6;
+                if (c_l >= cw) continue;
+                const int n_l = r / PT, tap = r - n_l * PT;
+                const long gi = d.taps > 0 ? ((long)(n0 + n_l) * PT + tap) * d.cpad + c0 + c_l : (long)(n0 + n_l) * d.cin + c0 + c_l;
+                const float g = d.g[gi];
+                acc += g * g;
+            }
+        }
+    } else {
+        const long base = (long)lb * ADAM_ELEMS;
+        const unsigned char* live = d.taps == 0 ? d.row_live : nullptr;     // rows that never had a gradient hold zeros: not read
+        for (int e = threadIdx.x; e < ADAM_ELEMS; e += 256) {
+            const long i = base + e;
+            if (i >= d.n) break;
+            if (live && !live[i / d.row_len]) continue;
+            long gi = i;
+            if (d.taps > 0) {
+                const long per_n = (long)d.cin * d.taps;
+                const long n = i / per_n;
+                const int r = (int)(i - n * per_n);
+                const int c = r / d.taps, tap = r - c * d.taps;
+                gi = (n * d.taps + tap) * d.cpad + c;
+            }
+            const float g = d.g[gi];
+            acc += g * g;
+        }
+    }
+    __shared__ float s_wave[4];
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[bid] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+extern "C" int cris_grad_sumsq(const cris_adam_desc* dev_table, int n_desc, int total_blocks, float* partials, void* stream) {
+    CRIS_CHECK_ARG(dev_table && n_desc > 0 && total_blocks > 0, "empty table");
+    CRIS_CHECK_ARG(partials, "null partials");
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, dev_table, n_desc, partials);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
+// out[0] = norm = grad_scale * sqrt(sum of the partials), out[1] = the divisor that clips to max_norm (1 when max_norm is
+// infinite): thread t adds partials t, t + 256, ... in double, thread 0 adds the 256 sums in thread order
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const float* __restrict__ partials, int n, float grad_scale, float max_norm,
+                                                                 float* __restrict__ out) {
+    __shared__ double s_sum[256];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) a += (double)partials[i];
+    s_sum[threadIdx.x] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int t = 0; t < 256; ++t) s += s_sum[t];
+        const double norm = (double)grad_scale * sqrt(s);
+        const float div = (float)((norm + 1e-6) / (double)max_norm);
+        out[0] = (float)norm;
+        // a non-finite norm gives a non-finite divisor (clip_grad_norm_ with error_if_nonfinite=False): NaN fails `<=` and is kept
+        out[1] = (isinf(max_norm) || div <= 1.f) ? 1.f : div;
+    }
+}
+extern "C" int cris_grad_clip_finalize(const float* partials, int n_partials, float grad_scale, float max_norm, float* out, void* stream) {
+    CRIS_CHECK_ARG(out && n_partials >= 0 && (partials || n_partials == 0), "bad args");      // no partials (an empty table): norm 0
+    CRIS_CHECK_ARG(max_norm > 0.f, "max_norm must be positive (infinity: norm only, divisor 1)");
+    hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, grad_scale, max_norm, out);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
 // counter[0] += 1 unless skip[0] != 0: the optimizer's step count under a GradScaler that may skip the step (found_inf)
 __global__ void counter_advance_unless_kernel(int32_t* counter, const float* skip) {
     if (!(skip && skip[0] != 0.f)) counter[0] += 1;

@@ -357,6 +357,8 @@ _SIGS = {
     "cris_adam_blocks": (I, [P]),
     "cris_adam_block_elems": (I, []),
     "cris_unpack_grads": (I, [P, I, I, P]),
+    "cris_grad_sumsq": (I, [P, I, I, P, P]),
+    "cris_grad_clip_finalize": (I, [P, I, F, F, P, P]),
     "cris_p2p_mailbox_bytes": (C.c_size_t, [I, I, I]),
     "cris_p2p_alloc": (I, [C.c_size_t, P]),
     "cris_p2p_free": (I, [P]),
@@ -396,7 +398,7 @@ class HipLibraryError(RuntimeError):
     pass
 
 
-ABI_VERSION = 6      # == CRIS_ABI_VERSION of include/cris_hip.h (tests/test_abi.py compares the two)
+ABI_VERSION = 7      # == CRIS_ABI_VERSION of include/cris_hip.h (tests/test_abi.py compares the two)
 
 
 def load():

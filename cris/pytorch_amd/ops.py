@@ -1003,6 +1003,10 @@ class AdamTable:
         self.row_live = dict(row_live) if row_live else {}
         self.keep = [pk[:2] for pk in self.packs if pk is not None]
         self.step_count = 0
+        # grad_norm(): one partial sum of squares per block of either table, and [norm, divisor] - allocated once (stable
+        # addresses for graph replay)
+        self._partials = torch.empty(max(sum(t.total_blocks for t in self.tables.values()), 1), dtype=torch.float32, device=self.device)
+        self.gnorm = torch.tensor([0.0, 1.0], dtype=torch.float32, device=self.device)
 
     def set_lrs(self, lrs):
         self.lrs = list(lrs)
@@ -1015,6 +1019,24 @@ class AdamTable:
     @property
     def refreshes_packs(self):
         return any(pk is not None for pk in self.packs)
+
+    def grad_norm(self, grad_scale=1.0, max_norm=None):
+        """fp32[2] device tensor owned by the table (overwritten by the next call): [0] = grad_scale * the 2-norm of all the
+        table's gradients taken as one vector (padding columns of GEMM-layout gradients excluded), [1] = the divisor that clips
+        it to max_norm, max(1, (norm + 1e-6) / max_norm) - torch.nn.utils.clip_grad_norm_'s coefficient inverted; pass
+        `[1:2]` to step() as loss_scale_dev.  max_norm=None: the norm only, divisor 1.  Three launches, no host sync,
+        deterministic (cris_grad_sumsq / cris_grad_clip_finalize)."""
+        if max_norm is not None and not max_norm > 0:
+            raise ValueError("max_norm must be positive (None: norm only), got %r" % (max_norm,))
+        off = 0
+        for taps in (9, 1):
+            t = self.tables[taps]
+            if t.n:
+                hip.call("cris_grad_sumsq", ptr(t.dev), t.n, t.total_blocks, ptr(self._partials[off:]), _stream())
+                off += t.total_blocks
+        hip.call("cris_grad_clip_finalize", ptr(self._partials), off, float(grad_scale),
+                 float("inf") if max_norm is None else float(max_norm), ptr(self.gnorm), _stream())
+        return self.gnorm
 
     def step(self, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0, step_dev=None, loss_scale_dev=None, skip_dev=None):
         """step_dev: optional int32 device tensor holding the 1-based step count (graph replay); else a host counter.

@@ -60,7 +60,14 @@ def epoch_group_lrs(epoch, base_lr, lr_multi, milestones, gamma):
 
 class NativeTrainer:
     def __init__(self, clip: ClipSpec, head: HeadSpec, state_dict, device, base_lr=1e-4, lr_multi=0.1, weight_decay=0.0,
-                 comm=None, sync_bn=False, use_graph: Optional[bool] = None, launch: Optional[str] = None):
+                 comm=None, sync_bn=False, use_graph: Optional[bool] = None, launch: Optional[str] = None, max_norm: float = 0.0,
+                 track_grad_norm: bool = False):
+        """max_norm > 0: clip the gradients by their global 2-norm like the reference's `clip_grad_norm_(model.parameters(),
+        args.max_norm)` (engine/engine.py:54-55); 0 (the shipped configs): no clipping.  track_grad_norm: compute `grad_norm`
+        every step without clipping."""
+        if not max_norm >= 0:
+            raise ValueError("max_norm must be >= 0 (0 = no clipping), got %r" % (max_norm,))
+        self.max_norm, self.track_grad_norm = float(max_norm), bool(track_grad_norm)
         self.device = device
         params, buffers = split_state_dict(state_dict, device)
         self.engine = Engine(clip, head, params, buffers, device, comm=comm, sync_bn=sync_bn)
@@ -165,6 +172,22 @@ class NativeTrainer:
         self._graph = self._cmds = None          # learning rates live in the device table, which was re-uploaded (new
         self._eager_steps = 0                    # address): capture / record again
 
+    def set_max_norm(self, max_norm):
+        """change the clipping threshold (0 = off); it is an argument of a launch, so the step is captured / recorded again"""
+        if not max_norm >= 0:
+            raise ValueError("max_norm must be >= 0 (0 = no clipping), got %r" % (max_norm,))
+        self.max_norm = float(max_norm)
+        self._graph = self._cmds = None
+        self._eager_steps = 0
+
+    @property
+    def grad_norm(self):
+        """2-norm of the last step's (rank-averaged, unclipped) gradient: a 0-dim device tensor, overwritten by the next step.
+        Only computed when max_norm > 0 or track_grad_norm is set."""
+        if not (self.max_norm > 0 or self.track_grad_norm):
+            raise RuntimeError("grad_norm is computed only with max_norm > 0 or track_grad_norm=True")
+        return self.adam.gnorm[0]
+
     def set_epoch(self, epoch, milestones=(35,), gamma=0.1):
         """Learning rates of the reference schedule for `epoch` (0-based); call at every epoch boundary."""
         self.set_group_lrs(*epoch_group_lrs(epoch, self.base_lr, self.lr_multi, milestones, gamma))
@@ -200,7 +223,14 @@ class NativeTrainer:
         else:
             e.backward()
         # one Adam pass over every tensor; it also rewrites the bf16 operand copies of the GEMM weights from the new values
-        self.adam.step(weight_decay=self.weight_decay, grad_scale=1.0 / self.comm.world, step_dev=self.step_dev)
+        divisor = None
+        if self.max_norm > 0 or self.track_grad_norm:
+            # clip_grad_norm_ (engine/engine.py:54-55) as a divisor of the update: the norm of the averaged gradient and
+            # max(1, norm / max_norm) are left on the device, the Adam kernels divide by it where GradScaler's scale goes
+            gn = self.adam.grad_norm(grad_scale=1.0 / self.comm.world, max_norm=self.max_norm if self.max_norm > 0 else None)
+            if self.max_norm > 0:
+                divisor = gn[1:2]
+        self.adam.step(weight_decay=self.weight_decay, grad_scale=1.0 / self.comm.world, step_dev=self.step_dev, loss_scale_dev=divisor)
         e.packs_current = self.adam.refreshes_packs
         return loss, pred, msk
 

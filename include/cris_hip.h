@@ -24,10 +24,10 @@ extern "C" {
 typedef uint16_t cris_bf16;
 
 const char* cris_last_error(void);
-/* CRIS_ABI_VERSION moves whenever an exported signature or struct changes; a binding compares cris_abi_version() with the
+/* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch */
-#define CRIS_ABI_VERSION 6
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize */
+#define CRIS_ABI_VERSION 7
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
 int cris_sizeof(const char* struct_name);
@@ -569,6 +569,20 @@ int cris_adam_blocks(const cris_adam_desc* d);       /* blocks one descriptor oc
 int cris_adam_block_elems(void);
 /* dst (param layout, desc.p) <- src (GEMM layout, desc.g) for a table of tensors; block_start as for cris_adam_step */
 int cris_unpack_grads(const cris_adam_desc* dev_table, int n_desc, int total_blocks, void* stream);
+/* Global gradient norm and the clipping divisor of torch.nn.utils.clip_grad_norm_ (engine/engine.py:54-55), over the tables
+ * cris_adam_step takes and in its block partition: block b (block_start / cris_adam_blocks) writes partials[b] = sum of g^2 over
+ * the elements that block updates, g read where the update reads it - parameter layout when taps == 0, else [n][tap][cpad], of
+ * which only the c < cin entries count (the padding columns are never read).  Rows with row_live == 0 are not read (they hold
+ * zeros).  Thread, wave and block sums are taken in a fixed order without atomics: the same bits on every run.  Call it once
+ * per table into disjoint ranges of one partials buffer, then cris_grad_clip_finalize once over all of it:
+ *   out[0] = norm = grad_scale * sqrt(sum of the partials)  (partials added in double, fixed order; grad_scale = the 1/world
+ *            the update applies, so the norm is that of the averaged gradient)
+ *   out[1] = max(1, (norm + 1e-6) / max_norm) = 1 / clamp(max_norm / (norm + 1e-6), max=1), the divisor to hand to
+ *            cris_adam_step_amp as loss_scale_dev; exactly 1 when nothing is clipped; non-finite when the norm is (the update
+ *            then writes NaN, as the reference's error_if_nonfinite=False does).  max_norm = +infinity: norm only, divisor 1;
+ *            max_norm <= 0 is an argument error.  n_partials == 0 (an empty table): norm 0, divisor 1. */
+int cris_grad_sumsq(const cris_adam_desc* dev_table, int n_desc, int total_blocks, float* partials, void* stream);
+int cris_grad_clip_finalize(const float* partials, int n_partials, float grad_scale, float max_norm, float* out, void* stream);
 
 /* ---- The sentence-vector path in fp32 (csrc/smallf32.hip) ----------------------------------------------------------------
  * At most CRIS_SMALL_MAX_ROWS (= the per-GPU batch) rows: LayerNorm of the end-of-text rows (model/clip.py:449-452), `@
