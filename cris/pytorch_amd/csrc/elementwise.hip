@@ -418,6 +418,76 @@ extern "C" int cris_step_advance(int32_t* step, uint32_t* seed, int32_t* exchang
     CRIS_LAUNCH_CHECK();
     return 0;
 }
+// micro-batch `micro` of `accum` of one optimizer step (gradient accumulation): the step counts optimizer steps, the dropout seed
+// and the mailbox generation advance with every forward pass
+__global__ void step_advance_micro_kernel(int* step, uint32_t* seed, int* exchange_gen, int micro, int accum) {
+    int s = step[0];                             // micro 0: steps completed so far; later micro-batches: that + 1 already
+    if (micro == 0) step[0] = s + 1;
+    else s -= 1;
+    seed[0] = ((uint32_t)s * (uint32_t)accum + (uint32_t)micro) * 7919u + 17u;      // accum == 1: cris_step_advance's rule
+    if (exchange_gen) exchange_gen[0] += 1;     // never repeats (p2p_ll.h): every micro-batch runs its own SyncBN exchanges
+}
+extern "C" int cris_step_advance_micro(int32_t* step, uint32_t* seed, int32_t* exchange_gen, int micro, int accum, void* stream) {
+    CRIS_CHECK_ARG(step && seed && accum >= 1 && micro >= 0 && micro < accum, "bad args (0 <= micro < accum)");
+    hipLaunchKernelGGL(step_advance_micro_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, seed, exchange_gen, micro, accum);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+// Gradient accumulation over arena ranges: dst = src (MODE 0) or dst += src (MODE 1), a pure HBM stream.  16 bytes per lane, two
+// independent vectors per thread and trip (all loads of a trip are issued before its first add), grid-stride over a grid sized
+// from the CU count.  One thread owns an output element: no atomics, one correctly rounded add - bit-reproducible.  The four
+// components are added one by one (no packed-FP32 VALU instructions: build.py FLAGS).
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float4* __restrict__ dst, const float4* __restrict__ src, long nvec) {
+    const long stride = (long)gridDim.x * 256;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    for (; i + stride < nvec; i += 2 * stride) {
+        float4 s0 = src[i], s1 = src[i + stride];
+        if (MODE == 1) {
+            const float4 d0 = dst[i], d1 = dst[i + stride];
+            s0.x = d0.x + s0.x; s0.y = d0.y + s0.y; s0.z = d0.z + s0.z; s0.w = d0.w + s0.w;
+            s1.x = d1.x + s1.x; s1.y = d1.y + s1.y; s1.z = d1.z + s1.z; s1.w = d1.w + s1.w;
+        }
+        dst[i] = s0;
+        dst[i + stride] = s1;
+    }
+    if (i < nvec) {
+        float4 s0 = src[i];
+        if (MODE == 1) {
+            const float4 d0 = dst[i];
+            s0.x = d0.x + s0.x; s0.y = d0.y + s0.y; s0.z = d0.z + s0.z; s0.w = d0.w + s0.w;
+        }
+        dst[i] = s0;
+    }
+}
+// compute units of the current device (queried once per device; no stream operation, so legal during a capture)
+static int cris_cu_count() {
+    static int cached[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!cached[dev]) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        cached[dev] = cus;
+    }
+    return cached[dev];
+}
+extern "C" int cris_grad_accumulate(float* dst, const float* src, long n, int mode, void* stream) {
+    CRIS_CHECK_ARG(dst && src && n > 0 && !(n & 3), "n must be a positive multiple of 4");
+    CRIS_CHECK_ARG(!(((uintptr_t)dst | (uintptr_t)src) & 15), "dst and src must be 16-byte aligned");
+    CRIS_CHECK_ARG(mode == 0 || mode == 1, "mode must be 0 (dst = src) or 1 (dst += src)");
+    CRIS_CHECK_ARG(dst + n <= src || src + n <= dst, "dst and src overlap");
+    const long nvec = n >> 2;
+    // at most 8 blocks of 256 threads per CU (the grid-stride loop takes the rest); a small range gets a block per 512 vectors, so
+    // that every thread still has two independent vectors in flight
+    const int grid = cris_grid_1d(nvec, 512, 8 * cris_cu_count());
+    if (mode == 0)
+        hipLaunchKernelGGL(grad_accumulate_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (float4*)dst, (const float4*)src, nvec);
+    else
+        hipLaunchKernelGGL(grad_accumulate_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (float4*)dst, (const float4*)src, nvec);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
 __global__ void axpy_f32_kernel(float* dst, const float* src, float alpha, long n) {
     GRID_STRIDE(i, n) dst[i] += alpha * src[i];
 }

@@ -315,7 +315,9 @@ _SIGS = {
     "cris_cast_bf16_f32": (I, [P, P, L, I, P]),
     "cris_cast_f32_bf16_drop": (I, [P, P, L, F, U, U, U, P, P]),
     "cris_step_advance": (I, [P, P, P, P]),
+    "cris_step_advance_micro": (I, [P, P, P, I, I, P]),
     "cris_axpy_f32": (I, [P, P, F, L, P]),
+    "cris_grad_accumulate": (I, [P, P, L, I, P]),
     "cris_quickgelu_fwd": (I, [P, P, L, P]),
     "cris_quickgelu_bwd": (I, [P, P, P, L, P]),
     "cris_embed_fwd": (I, [P, P, P, I, I, I, P, P]),
@@ -398,7 +400,7 @@ class HipLibraryError(RuntimeError):
     pass
 
 
-ABI_VERSION = 7      # == CRIS_ABI_VERSION of include/cris_hip.h (tests/test_abi.py compares the two)
+ABI_VERSION = 8      # == CRIS_ABI_VERSION of include/cris_hip.h (tests/test_abi.py compares the two)
 
 
 def load():

@@ -769,6 +769,19 @@ def step_advance(step, seed, exchange_gen=None):
     hip.call("cris_step_advance", ptr(step), ptr(seed), ptr(exchange_gen), _stream())
 
 
+def step_advance_micro(step, seed, exchange_gen, micro, accum):
+    """per-micro-batch device state of an accumulating step: the step counts optimizer steps (advanced by micro-batch 0), the
+    dropout seed is (s * accum + micro) * 7919 + 17, the mailbox generation advances with every micro-batch"""
+    hip.call("cris_step_advance_micro", ptr(step), ptr(seed), ptr(exchange_gen), int(micro), int(accum), _stream())
+
+
+def grad_accumulate(dst, src, add=True):
+    """dst += src (add=False: dst = src) over two disjoint, 16-byte-aligned fp32 ranges of equal length (a multiple of 4): one
+    rounding per element, bit-reproducible"""
+    assert dst.dtype == src.dtype == torch.float32 and dst.numel() == src.numel()
+    hip.call("cris_grad_accumulate", ptr(dst), ptr(src), dst.numel(), 1 if add else 0, _stream())
+
+
 def counter_advance(counter, skip=None):
     """counter[0] += 1 on the device (unless skip[0] != 0)"""
     hip.call("cris_counter_advance_unless", ptr(counter), ptr(skip), _stream())

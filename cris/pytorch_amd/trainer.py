@@ -18,7 +18,15 @@ while every library call (function pointer + ctypes arguments) and every torch-l
 recorded, with all of its buffers allocated from a private torch MemPool so their addresses stay valid; later steps
 replay the list - a few microseconds of Python per launch, collectives issued by torch.distributed as usual.
 `launch=` / CRIS_LAUNCH selects "graph", "cmdlist" or "eager" explicitly.
+
+Gradient accumulation (`accum_steps=K`): train_step takes the whole optimizer batch of K*b samples and runs K forward/backward
+passes over its K equal slices from the same parameters - the usual `for chunk: (loss_chunk / K).backward()`, then clip, then
+`optimizer.step()`.  The sum is kept in a second arena-sized buffer `acc` and built per arena stage from the backward's stage
+hook: acc = g0, acc += g1, ..., and in the last micro-batch g += acc, so the total ((g0 + g1) + g2) + ... + g_{K-1} (one fp32
+rounding per add, in this order) ends up in the gradient arena, where the exchange, the norm, Adam and grads_param_layout() read
+it.  The 1/K goes where 1/world goes (the update's grad_scale).  All K passes are part of ONE captured graph / command list.
 """
+import contextlib
 import os
 from typing import Optional
 
@@ -61,13 +69,15 @@ def epoch_group_lrs(epoch, base_lr, lr_multi, milestones, gamma):
 class NativeTrainer:
     def __init__(self, clip: ClipSpec, head: HeadSpec, state_dict, device, base_lr=1e-4, lr_multi=0.1, weight_decay=0.0,
                  comm=None, sync_bn=False, use_graph: Optional[bool] = None, launch: Optional[str] = None, max_norm: float = 0.0,
-                 track_grad_norm: bool = False):
-        """max_norm > 0: clip the gradients by their global 2-norm like the reference's `clip_grad_norm_(model.parameters(),
+                 track_grad_norm: bool = False, accum_steps: int = 1):
+        """accum_steps = K > 1: one train_step is one optimizer step over K micro-batches (the module docstring; set_accum_steps).
+        max_norm > 0: clip the gradients by their global 2-norm like the reference's `clip_grad_norm_(model.parameters(),
         args.max_norm)` (engine/engine.py:54-55); 0 (the shipped configs): no clipping.  track_grad_norm: compute `grad_norm`
         every step without clipping."""
         if not max_norm >= 0:
             raise ValueError("max_norm must be >= 0 (0 = no clipping), got %r" % (max_norm,))
         self.max_norm, self.track_grad_norm = float(max_norm), bool(track_grad_norm)
+        self.accum_steps = self._checked_accum(accum_steps)
         self.device = device
         params, buffers = split_state_dict(state_dict, device)
         self.engine = Engine(clip, head, params, buffers, device, comm=comm, sync_bn=sync_bn)
@@ -147,6 +157,8 @@ class NativeTrainer:
         self._eager_steps = 0
         self.graph_error = None
         self._host_steps = 0
+        self._acc = self._loss_acc = self._metric_micro = None
+        self.set_accum_steps(self.accum_steps)
         self._peer_check_every = int(os.environ.get("CRIS_PEER_CHECK_EVERY", "200"))
 
     def _build_adam(self, lrs):
@@ -180,9 +192,30 @@ class NativeTrainer:
         self._graph = self._cmds = None
         self._eager_steps = 0
 
+    @staticmethod
+    def _checked_accum(k):
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError("accum_steps must be an integer >= 1, got %r" % (k,))
+        return k
+
+    def set_accum_steps(self, accum_steps):
+        """number of micro-batches per optimizer step; the step is captured / recorded again.  K > 1 holds a second buffer of the
+        gradient arena's size (the running sum), K == 1 holds none and runs exactly the step of a trainer without accumulation.
+        The dropout seeds follow (step * K + micro) * 7919 + 17 with the K of the running step."""
+        self.accum_steps = self._checked_accum(accum_steps)
+        if self.accum_steps > 1:
+            if self._acc is None:
+                self._acc = torch.empty_like(self.engine.grad_arena)
+                self._loss_acc = torch.zeros((), device=self.device)
+                self._metric_micro = torch.zeros(2, device=self.device)
+        else:
+            self._acc = self._loss_acc = self._metric_micro = None
+        self._graph = self._cmds = None
+        self._eager_steps = 0
+
     @property
     def grad_norm(self):
-        """2-norm of the last step's (rank-averaged, unclipped) gradient: a 0-dim device tensor, overwritten by the next step.
+        """2-norm of the last step's (rank- and micro-batch-averaged, unclipped) gradient: a 0-dim device tensor, overwritten by the next step.
         Only computed when max_norm > 0 or track_grad_norm is set."""
         if not (self.max_norm > 0 or self.track_grad_norm):
             raise RuntimeError("grad_norm is computed only with max_norm > 0 or track_grad_norm=True")
@@ -195,6 +228,8 @@ class NativeTrainer:
     # ------------------------------------------------------------------------------------------------
     def _step_body(self, img, word, mask, host_seed: Optional[int]):
         e = self.engine
+        if self.accum_steps > 1:
+            return self._step_body_accum(img, word, mask, host_seed)
         if host_seed is None:
             ops.step_advance(self.step_dev, self.seed_dev, self.xgen_dev)
             e.seed_dev, seed = self.seed_dev, 0
@@ -234,9 +269,64 @@ class NativeTrainer:
         e.packs_current = self.adam.refreshes_packs
         return loss, pred, msk
 
+    def _step_body_accum(self, img, word, mask, host_seed: Optional[int]):
+        """the step over K = accum_steps micro-batches (views of the inputs' K equal slices); see the module docstring"""
+        e, K = self.engine, self.accum_steps
+        b = img.shape[0] // K
+        exchange = self.comm.world > 1 or debug.HOOKS.force_dist
+        ops.zero_(self._loss_acc)
+        ops.zero_(self.metric)
+        for m in range(K):
+            last = m == K - 1
+            # the step counter advances with micro-batch 0, the seed and the mailbox generation with every micro-batch
+            ops.step_advance_micro(self.step_dev, self.seed_dev, self.xgen_dev, m, K)
+            if host_seed is None:
+                e.seed_dev, seed = self.seed_dev, 0
+            else:                                # explicit seed (tests): seed + m for micro-batch m
+                e.seed_dev, seed = None, host_seed + m
+            sl = slice(m * b, (m + 1) * b)
+            pred, msk, loss = e.forward(img[sl], word[sl], mask[sl], training=True, seed=seed)
+            ops.axpy_f32(self._loss_acc, loss, 1.0 / K)
+            # mean of the micro-batches' metrics = the whole batch's (equal sizes); on the text-encoder stream like the K = 1 step
+            if e.side is not None:
+                cur = torch.cuda.current_stream()
+                ops.torch_op(lambda: e.side.wait_stream(cur))
+            with (torch.cuda.stream(e.side) if e.side is not None else contextlib.nullcontext()):
+                ops.train_metric(pred, msk, pred.shape[0], pred.shape[2] * pred.shape[3], self._metric_micro)
+                ops.axpy_f32(self.metric, self._metric_micro, 1.0 / K)
+
+            def on_stage(st, m=m, last=last):
+                # fires on the stream the stage's gradients were issued on (stage 4: the side stream)
+                lo, hi = e.stage_ranges[st]
+                g, acc = e.grad_arena[lo:hi], self._acc[lo:hi]
+                if not last:
+                    ops.grad_accumulate(acc, g, add=m > 0)       # acc = g0 ; acc += g_m
+                    return
+                ops.grad_accumulate(g, acc)                      # the total, in the arena, before the stage's exchange
+                if exchange:
+                    ops.torch_op(lambda: self.comm.allreduce_async(g))
+                    if st == 4 and e.embed_live is not None and getattr(self.comm, "supports_max_u8", False):
+                        # (sticky marks: the rows of every micro-batch of this step, and of every step before)
+                        ops.torch_op(lambda: self.comm.allreduce_async(e.embed_live, op="max"))
+            e.backward(on_stage_done=on_stage)
+        if exchange:
+            ops.torch_op(self.comm.wait_all)
+        scale = 1.0 / (self.comm.world * K)
+        divisor = None
+        if self.max_norm > 0 or self.track_grad_norm:
+            gn = self.adam.grad_norm(grad_scale=scale, max_norm=self.max_norm if self.max_norm > 0 else None)
+            if self.max_norm > 0:
+                divisor = gn[1:2]
+        self.adam.step(weight_decay=self.weight_decay, grad_scale=scale, step_dev=self.step_dev, loss_scale_dev=divisor)
+        e.packs_current = self.adam.refreshes_packs
+        return self._loss_acc, pred, msk
+
     def train_step(self, img, word, mask, seed: Optional[int] = None):
         """One optimizer step.  Returns (loss 0-dim device tensor, metric [IoU%, Pr@50%] device tensor); both are
-        overwritten by the next call."""
+        overwritten by the next call.  With accum_steps = K > 1 the inputs hold the whole optimizer batch of K * b samples,
+        micro-batch m is samples [m*b, (m+1)*b), and loss and metric are the means over the K micro-batches."""
+        if img.shape[0] % self.accum_steps:
+            raise ValueError("batch of %d samples is not a multiple of accum_steps = %d" % (img.shape[0], self.accum_steps))
         # COLLECTIVE, every CRIS_PEER_CHECK_EVERY-th step (default 200; 0 = never): a rank whose SyncBN mailbox exchange gave up
         # waiting for a peer raises on EVERY rank instead of training on alone (round-5 advisor finding: nothing called the check)
         self._host_steps += 1
@@ -305,11 +395,13 @@ class NativeTrainer:
     def model_state_dict(self, ddp_prefix=False):
         """the reference module's `state_dict()` (parameters + BatchNorm buffers; clones, on the CPU).  `ddp_prefix=True`:
         keys spelled `module.<name>` like the checkpoints the reference writes from its DDP-wrapped model
-        (train.py:192-204) - what its `--resume` (train.py:159-174) and test.py:74-78 load strictly."""
+        (train.py:192-204) - what its `--resume` (train.py:159-174) and test.py:74-78 load strictly.
+        `num_batches_tracked` counts forward passes, step_idx * accum_steps: exact only while accum_steps has not changed
+        during the run."""
         e = self.engine
         out = {k: v.detach().cpu().clone() for k, v in e.P.items()}
         out.update({k: v.detach().cpu().clone() for k, v in e.Bf.items()})
-        steps = self.step_idx
+        steps = self.step_idx * self.accum_steps         # forward passes (exact while accum_steps has not changed during the run)
         for pfx in e.bn_prefixes:
             out[pfx + ".num_batches_tracked"] = torch.tensor(steps, dtype=torch.int64)
         # reference key order (module order), not "parameters then buffers"

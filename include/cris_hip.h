@@ -26,8 +26,8 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize */
-#define CRIS_ABI_VERSION 7
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro */
+#define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
 int cris_sizeof(const char* struct_name);
@@ -432,7 +432,15 @@ int cris_cast_f32_bf16_drop(const float* x, cris_bf16* y, long n, float drop_p, 
 /* device-side per-step state of a replayed HIP graph: seed[0] = step[0] * 7919 + 17 ; step[0] += 1 ; exchange_gen[0] += 1
  * (exchange_gen may be NULL: the generation counter of the peer-mailbox exchanges, never rewound - see csrc/p2p_ll.h) */
 int cris_step_advance(int32_t* step, uint32_t* seed, int32_t* exchange_gen, void* stream);
+/* the same for micro-batch `micro` (0-based) of `accum` of one optimizer step (gradient accumulation): step[0] += 1 only when micro == 0,
+ * seed[0] = (s * accum + micro) * 7919 + 17 with s = optimizer steps completed before this step, exchange_gen[0] += 1 on EVERY
+ * micro-batch (each runs its own SyncBN exchanges).  accum == 1 gives cris_step_advance's values. */
+int cris_step_advance_micro(int32_t* step, uint32_t* seed, int32_t* exchange_gen, int micro, int accum, void* stream);
 int cris_axpy_f32(float* dst, const float* src, float alpha, long n, void* stream);
+/* gradient accumulation over a range of the fp32 gradient arena: mode 0: dst[i] = src[i] (first micro-batch: starts the sum, no
+ * memset), mode 1: dst[i] += src[i] (one correctly rounded fp32 add per element, each written by exactly one thread: bit-reproducible).
+ * n a multiple of 4, both pointers 16-byte aligned, ranges disjoint.  16-byte accesses, grid-stride, grid sized from the CU count. */
+int cris_grad_accumulate(float* dst, const float* src, long n, int mode, void* stream);
 /* QuickGELU x*sigmoid(1.702x) on a stored bf16 pre-activation (model/clip.py:234-236) */
 int cris_quickgelu_fwd(const cris_bf16* x, cris_bf16* y, long n, void* stream);
 int cris_quickgelu_bwd(const cris_bf16* x, const cris_bf16* dy, cris_bf16* dx, long n, void* stream);
