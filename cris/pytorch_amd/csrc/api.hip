@@ -33,6 +33,7 @@ extern "C" int cris_sizeof(const char* name) {
     S(cris_sum_group);
     S(cris_attn_params);
     S(cris_adam_desc);
+    S(cris_ema_desc);
     S(cris_p2p_params);
     S(cris_p2p_link);
     S(cris_p2p_arena_params);

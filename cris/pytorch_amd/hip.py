@@ -193,6 +193,10 @@ class AdamDesc(C.Structure):
                 ("row_live", P), ("row_len", I), ("ldD", I)]
 
 
+class EmaDesc(C.Structure):
+    _fields_ = [("p", P), ("ema", P), ("n", L), ("row_live", P), ("row_len", I), ("block_start", I)]
+
+
 ZERO_RANGES_MAX = 16
 
 
@@ -249,7 +253,7 @@ STRUCTS = {
     "cris_conv_gemm_params": ConvGemmParams, "cris_conv_gemm_group": ConvGemmGroup, "cris_wgrad_params": WgradParams, "cris_wgrad_group": WgradGroup, "cris_pack_desc": PackDesc,
     "cris_conv_gemm_fp8_params": ConvGemmFp8Params, "cris_pack_fp8_desc": PackFp8Desc,
     "cris_bn_apply_params": BnApplyParams, "cris_bn_bwd_params": BnBwdParams, "cris_ln_fwd_params": LnFwdParams,
-    "cris_ln_bwd_params": LnBwdParams, "cris_sum_entry": SumEntry, "cris_sum_group": SumGroup, "cris_attn_params": AttnParams, "cris_adam_desc": AdamDesc, "cris_p2p_params": P2PParams, "cris_p2p_link": P2PLink, "cris_p2p_arena_params": P2PArenaParams, "cris_zero_ranges": ZeroRanges,
+    "cris_ln_bwd_params": LnBwdParams, "cris_sum_entry": SumEntry, "cris_sum_group": SumGroup, "cris_attn_params": AttnParams, "cris_adam_desc": AdamDesc, "cris_ema_desc": EmaDesc, "cris_p2p_params": P2PParams, "cris_p2p_link": P2PLink, "cris_p2p_arena_params": P2PArenaParams, "cris_zero_ranges": ZeroRanges,
     "cris_sample_desc": SampleDesc, "cris_eval_desc": EvalDesc, "cris_jpeg_info": JpegInfo, "cris_jpeg_image": JpegImage,
 }
 
@@ -361,6 +365,9 @@ _SIGS = {
     "cris_unpack_grads": (I, [P, I, I, P]),
     "cris_grad_sumsq": (I, [P, I, I, P, P]),
     "cris_grad_clip_finalize": (I, [P, I, F, F, P, P]),
+    "cris_ema_blocks": (I, [P]),
+    "cris_ema_advance": (I, [P, I, F, I, P, P]),
+    "cris_ema_update": (I, [P, I, I, P, P]),
     "cris_p2p_mailbox_bytes": (C.c_size_t, [I, I, I]),
     "cris_p2p_alloc": (I, [C.c_size_t, P]),
     "cris_p2p_free": (I, [P]),

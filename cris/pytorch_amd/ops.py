@@ -1065,6 +1065,87 @@ class AdamTable:
                          grad_scale, ptr(step_dev), ptr(loss_scale_dev), ptr(skip_dev), taps, _stream())
 
 
+def ema_weight(t, decay, warmup=False):
+    """host mirror of cris_ema_advance in numpy float32: the weight 1 - d of EMA update number t (0-based),
+    d = min(decay, (1 + t) / (10 + t)) with warm-up, else decay"""
+    import numpy as np
+    d = np.float32(decay)
+    if warmup:
+        w = (np.float32(1.0) + np.float32(t)) / (np.float32(10.0) + np.float32(t))
+        d = w if w < d else d
+    return np.float32(1.0) - d
+
+
+class EmaTable:
+    """Exponential moving average of a set of fp32 tensors, kept on the device: one flat fp32 buffer (every tensor's slice starts
+    on a 16-byte boundary), the device table of cris_ema_desc and the 16-byte state record {updates, weight, active, pad}.  All
+    three keep their addresses for the table's lifetime (graph replay).  update() is two launches, whatever the number of tensors."""
+
+    def __init__(self, named, row_live=None, guard=0):
+        """named: (name, tensor) pairs - contiguous fp32 device tensors, read in place.  row_live: {name: uint8 tensor [rows]} -
+        rows of that 2-d tensor whose byte is 0 are skipped (cris_ema_desc.row_live).  guard: unused floats (rounded up to a
+        multiple of 4) in front of, between and behind the slices.  The average starts undefined: call reset()."""
+        lib = hip.load()
+        self.named = [(n, t) for n, t in named]
+        assert self.named, "empty EMA table"
+        self.device = self.named[0][1].device
+        guard = (int(guard) + 3) // 4 * 4
+        self.offsets, off = {}, guard
+        for n, t in self.named:
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() > 0 and n not in self.offsets, n
+            self.offsets[n] = off
+            off += (t.numel() + 3) // 4 * 4 + guard
+        self.flat = torch.zeros(off, dtype=torch.float32, device=self.device)
+        assert self.flat.data_ptr() % 16 == 0
+        self.views = {n: self.flat[self.offsets[n]:self.offsets[n] + t.numel()].view(t.shape) for n, t in self.named}
+        self.state = torch.zeros(4, dtype=torch.int32, device=self.device)       # {updates, weight (fp32 bits), active, pad}
+        self.row_live = dict(row_live) if row_live else {}
+        self.arr = (hip.EmaDesc * len(self.named))()
+        start = 0
+        for d, (n, t) in zip(self.arr, self.named):
+            d.p, d.ema, d.n = ptr(t), ptr(self.views[n]), t.numel()
+            live = self.row_live.get(n)
+            if live is not None:
+                assert t.dim() == 2 and live.dtype == torch.uint8 and live.numel() == t.shape[0], n
+                d.row_live, d.row_len = ptr(live), t.shape[1]
+            d.block_start = start
+            nb = lib.cris_ema_blocks(C.byref(d))
+            if nb <= 0:
+                hip.check(nb if nb else -1, "cris_ema_blocks(%s)" % n)
+            start += nb
+        self.total_blocks = start
+        self.dev = torch.frombuffer(bytearray(bytes(self.arr)), dtype=torch.uint8).to(self.device)
+
+    @property
+    def num_elements(self):
+        return sum(t.numel() for _, t in self.named)
+
+    def reset(self, num_updates=0):
+        """ema = the tensors' current values; the update count restarts at num_updates (it selects the warm-up weight)"""
+        for n, t in self.named:
+            self.views[n].copy_(t)
+        self.state.copy_(torch.tensor([int(num_updates), 0, 0, 0], dtype=torch.int32))
+
+    @property
+    def num_updates(self):
+        return int(self.state[0].item())
+
+    def drop_row_live(self):
+        """update every row from now on (the table is rewritten in place: same address, same partition)"""
+        if not self.row_live:
+            return
+        self.row_live = {}
+        for d in self.arr:
+            d.row_live, d.row_len = None, 0
+        self.dev.copy_(torch.frombuffer(bytearray(bytes(self.arr)), dtype=torch.uint8))
+
+    def update(self, step_dev, every=1, decay=0.999, warmup=False):
+        """one EMA step, decided on the device: when step_dev[0] (1-based optimizer step) is a multiple of `every`,
+        ema += (p - ema) * weight with weight = 1 - decay (warm-up: ops.ema_weight); else nothing but the two launches"""
+        hip.call("cris_ema_advance", ptr(step_dev), int(every), float(decay), 1 if warmup else 0, ptr(self.state), _stream())
+        hip.call("cris_ema_update", ptr(self.dev), len(self.named), self.total_blocks, ptr(self.state), _stream())
+
+
 class UnpackTable:
     """Device table for cris_unpack_grads: GEMM-layout gradients (srcs) -> parameter-layout tensors (dsts)."""
 

@@ -25,6 +25,13 @@ passes over its K equal slices from the same parameters - the usual `for chunk: 
 hook: acc = g0, acc += g1, ..., and in the last micro-batch g += acc, so the total ((g0 + g1) + g2) + ... + g_{K-1} (one fp32
 rounding per add, in this order) ends up in the gradient arena, where the exchange, the norm, Adam and grads_param_layout() read
 it.  The 1/K goes where 1/world goes (the update's grad_scale).  All K passes are part of ONE captured graph / command list.
+
+Averaged weights (`ema_decay=d`): an exponential moving average of every parameter and every BatchNorm running statistic lives in
+one flat device buffer (ops.EmaTable) and is advanced at the end of the step, after Adam, by two launches that are part of the
+captured / recorded step: `cris_ema_advance` decides on the device whether this optimizer step is an EMA step (`ema_every`) and
+with which weight (`ema_warmup`), `cris_ema_update` applies ema += (p - ema) * weight to everything.  Once per optimizer step,
+not per micro-batch; no communication (parameters, hence averages, are identical on every rank).  ema_state_dict() has the keys
+of model_state_dict().  With ema_decay=None (the default) nothing is allocated and the step issues the launches it always did.
 """
 import contextlib
 import os
@@ -69,8 +76,11 @@ def epoch_group_lrs(epoch, base_lr, lr_multi, milestones, gamma):
 class NativeTrainer:
     def __init__(self, clip: ClipSpec, head: HeadSpec, state_dict, device, base_lr=1e-4, lr_multi=0.1, weight_decay=0.0,
                  comm=None, sync_bn=False, use_graph: Optional[bool] = None, launch: Optional[str] = None, max_norm: float = 0.0,
-                 track_grad_norm: bool = False, accum_steps: int = 1):
-        """accum_steps = K > 1: one train_step is one optimizer step over K micro-batches (the module docstring; set_accum_steps).
+                 track_grad_norm: bool = False, accum_steps: int = 1, ema_decay: Optional[float] = None, ema_every: int = 1,
+                 ema_warmup: bool = False):
+        """ema_decay = d in (0, 1): keep an exponential moving average of parameters and BatchNorm statistics, updated every
+        `ema_every`-th optimizer step with weight 1 - d (ema_warmup: 1 - min(d, (1 + t) / (10 + t)) for update t); set_ema.
+        accum_steps = K > 1: one train_step is one optimizer step over K micro-batches (the module docstring; set_accum_steps).
         max_norm > 0: clip the gradients by their global 2-norm like the reference's `clip_grad_norm_(model.parameters(),
         args.max_norm)` (engine/engine.py:54-55); 0 (the shipped configs): no clipping.  track_grad_norm: compute `grad_norm`
         every step without clipping."""
@@ -78,6 +88,7 @@ class NativeTrainer:
             raise ValueError("max_norm must be >= 0 (0 = no clipping), got %r" % (max_norm,))
         self.max_norm, self.track_grad_norm = float(max_norm), bool(track_grad_norm)
         self.accum_steps = self._checked_accum(accum_steps)
+        ema_cfg = self._checked_ema(ema_decay, ema_every, ema_warmup)
         self.device = device
         params, buffers = split_state_dict(state_dict, device)
         self.engine = Engine(clip, head, params, buffers, device, comm=comm, sync_bn=sync_bn)
@@ -159,6 +170,8 @@ class NativeTrainer:
         self._host_steps = 0
         self._acc = self._loss_acc = self._metric_micro = None
         self.set_accum_steps(self.accum_steps)
+        self._ema = None
+        self.set_ema(*ema_cfg)                   # (after the rank-0 broadcast above: the average starts from the shared values)
         self._peer_check_every = int(os.environ.get("CRIS_PEER_CHECK_EVERY", "200"))
 
     def _build_adam(self, lrs):
@@ -212,6 +225,41 @@ class NativeTrainer:
             self._acc = self._loss_acc = self._metric_micro = None
         self._graph = self._cmds = None
         self._eager_steps = 0
+
+    @staticmethod
+    def _checked_ema(decay, every, warmup):
+        if decay is not None and (isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 < decay < 1.0):
+            raise ValueError("ema_decay must be None (off) or a number in (0, 1), got %r" % (decay,))
+        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+            raise ValueError("ema_every must be an integer >= 1, got %r" % (every,))
+        return (None if decay is None else float(decay)), every, bool(warmup)
+
+    def set_ema(self, decay, every=1, warmup=False):
+        """switch the weight average on (0 < decay < 1), change its settings, or switch it off (None: the buffer is freed); the
+        step is captured / recorded again.  Switching it ON sets the average to the current parameters and BatchNorm statistics
+        and its update count to 0; changing decay / every / warmup of a running average keeps both.  Costs one more fp32 copy
+        of the parameters and buffers."""
+        self.ema_decay, self.ema_every, self.ema_warmup = self._checked_ema(decay, every, warmup)
+        if self.ema_decay is None:
+            self._ema = None
+        elif self._ema is None:
+            e = self.engine
+            name = "backbone.token_embedding.weight"
+            self._ema = ops.EmaTable(list(e.P.items()) + list(e.Bf.items()),
+                                     row_live={name: e.embed_live} if e.embed_live is not None else None)
+            self._ema.reset()
+        self._graph = self._cmds = None
+        self._eager_steps = 0
+
+    def _ema_table(self):
+        if self._ema is None:
+            raise RuntimeError("no weight average is kept: build the trainer with ema_decay or call set_ema(decay)")
+        return self._ema
+
+    @property
+    def ema_num_updates(self):
+        """EMA updates applied so far (selects the warm-up weight of the next one); reads the device counter"""
+        return self._ema_table().num_updates
 
     @property
     def grad_norm(self):
@@ -267,6 +315,8 @@ class NativeTrainer:
                 divisor = gn[1:2]
         self.adam.step(weight_decay=self.weight_decay, grad_scale=1.0 / self.comm.world, step_dev=self.step_dev, loss_scale_dev=divisor)
         e.packs_current = self.adam.refreshes_packs
+        if self._ema is not None:
+            self._ema.update(self.step_dev, self.ema_every, self.ema_decay, self.ema_warmup)
         return loss, pred, msk
 
     def _step_body_accum(self, img, word, mask, host_seed: Optional[int]):
@@ -319,6 +369,8 @@ class NativeTrainer:
                 divisor = gn[1:2]
         self.adam.step(weight_decay=self.weight_decay, grad_scale=scale, step_dev=self.step_dev, loss_scale_dev=divisor)
         e.packs_current = self.adam.refreshes_packs
+        if self._ema is not None:                # once per optimizer step, after the K-th micro-batch's update
+            self._ema.update(self.step_dev, self.ema_every, self.ema_decay, self.ema_warmup)
         return self._loss_acc, pred, msk
 
     def train_step(self, img, word, mask, seed: Optional[int] = None):
@@ -399,8 +451,16 @@ class NativeTrainer:
         `num_batches_tracked` counts forward passes, step_idx * accum_steps: exact only while accum_steps has not changed
         during the run."""
         e = self.engine
-        out = {k: v.detach().cpu().clone() for k, v in e.P.items()}
-        out.update({k: v.detach().cpu().clone() for k, v in e.Bf.items()})
+        return self._state_dict_of({k: v for k, v in list(e.P.items()) + list(e.Bf.items())}, ddp_prefix)
+
+    def ema_state_dict(self, ddp_prefix=False):
+        """the averaged weights in the form of model_state_dict(): same keys, same order, loadable wherever that one is
+        (InferenceRunner.load_state_dict, the reference's test.py); `num_batches_tracked` is the live model's"""
+        return self._state_dict_of(self._ema_table().views, ddp_prefix)
+
+    def _state_dict_of(self, tensors, ddp_prefix):
+        e = self.engine
+        out = {k: v.detach().cpu().clone() for k, v in tensors.items()}
         steps = self.step_idx * self.accum_steps         # forward passes (exact while accum_steps has not changed during the run)
         for pfx in e.bn_prefixes:
             out[pfx + ".num_batches_tracked"] = torch.tensor(steps, dtype=torch.int64)
@@ -424,6 +484,29 @@ class NativeTrainer:
         for k, t in list(e.P.items()) + list(e.Bf.items()):
             t.copy_(sd[k].to(self.device))
         e.packs_current = False
+        if self._ema is not None:                # the average restarts from the loaded weights (load_ema_state_dict overrides)
+            self._ema.reset()
+
+    def load_ema_state_dict(self, sd, num_updates):
+        """restore the averaged weights (ema_state_dict(); keys may carry `module.`) and the update count (ema_num_updates).
+        When resuming, call it after load_model_state_dict, which resets the average to the loaded weights."""
+        ema, e = self._ema_table(), self.engine
+        if isinstance(num_updates, bool) or not isinstance(num_updates, int) or num_updates < 0:
+            raise ValueError("num_updates must be an integer >= 0, got %r" % (num_updates,))
+        sd = strip_ddp_prefix(sd)
+        missing = [k for k in ema.views if k not in sd]
+        if missing:
+            raise KeyError("state_dict lacks %d keys, e.g. %s" % (len(missing), missing[:3]))
+        for k, v in ema.views.items():
+            v.copy_(sd[k].to(self.device))
+        ema.state.copy_(torch.tensor([num_updates, 0, 0, 0], dtype=torch.int32))
+        # the update skips embedding rows that never had a gradient because there ema == p; an average from elsewhere may differ
+        # from the parameters in such a row, and the skip would freeze that difference: then every row is updated from now on
+        for name, live in list(ema.row_live.items()):
+            dead = live == 0
+            if bool((ema.views[name][dead] != e.P[name][dead]).any()):
+                ema.drop_row_live()
+                break
 
     def optimizer_state_dict(self):
         """Adam state in torch.optim.Adam.state_dict() form, loadable by the optimizer `train.py:105-107` builds from

@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -591,6 +591,32 @@ int cris_unpack_grads(const cris_adam_desc* dev_table, int n_desc, int total_blo
  *            max_norm <= 0 is an argument error.  n_partials == 0 (an empty table): norm 0, divisor 1. */
 int cris_grad_sumsq(const cris_adam_desc* dev_table, int n_desc, int total_blocks, float* partials, void* stream);
 int cris_grad_clip_finalize(const float* partials, int n_partials, float grad_scale, float max_norm, float* out, void* stream);
+
+/* Exponential moving average of the weights, inside the step (csrc/ema.hip).  `state` is a 16-byte device record
+ * {int32 updates; float weight; int32 active; int32 pad}, 16-byte aligned.
+ * cris_ema_advance (one thread): step = step_dev[0], the 1-based optimizer step cris_step_advance[_micro] already advanced;
+ *   active = (step % every == 0).  When active: t = updates, updates += 1,
+ *   d = warmup ? min(decay, (1 + t) / (10 + t)) : decay  (fp32, correctly rounded division), weight = 1 - d.
+ *   When not active, updates and weight keep their values.  0 < decay < 1, every >= 1.
+ * cris_ema_update: one launch over a device table of cris_ema_desc.  active == 0: every block returns at once.  Otherwise per
+ *   element ema = ema + (p - ema) * weight as three separately rounded fp32 operations (no fused multiply-add), which torch's
+ *   `e.add_((p - e) * w)` reproduces bit for bit.  Each element is written by one thread.  Partition: block trip b owns
+ *   cris_adam_block_elems() consecutive elements of one tensor (block_start = prefix sums of cris_ema_blocks); the grid is capped
+ *   at 8 blocks per CU and strides over the trips.  16-byte accesses on whole vectors (p element by element when its start is
+ *   not 16-byte aligned), scalar code for the last n % 4 elements.
+ *   row_live (optional; row_len = elements per row): rows whose byte is 0 are neither read nor written.  For a parameter whose
+ *   row has never changed since ema was set to it, ema == p and ema + 0 * weight == ema: the same bits as the dense update.
+ * cris_ema_blocks (host): validates a descriptor (p, ema non-null, n > 0, ema 16-byte aligned, row_live only with row_len > 0)
+ *   and returns the block trips it occupies, -1 with cris_last_error() otherwise. */
+typedef struct {
+    const float* p; float* ema;
+    long n;
+    const unsigned char* row_live;
+    int row_len; int block_start;
+} cris_ema_desc;
+int cris_ema_blocks(const cris_ema_desc* d);
+int cris_ema_advance(const int32_t* step_dev, int every, float decay, int warmup, void* state, void* stream);
+int cris_ema_update(const cris_ema_desc* dev_table, int n_desc, int total_blocks, const void* state, void* stream);
 
 /* ---- The sentence-vector path in fp32 (csrc/smallf32.hip) ----------------------------------------------------------------
  * At most CRIS_SMALL_MAX_ROWS (= the per-GPU batch) rows: LayerNorm of the end-of-text rows (model/clip.py:449-452), `@
