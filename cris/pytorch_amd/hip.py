@@ -368,6 +368,7 @@ _SIGS = {
     "cris_ema_blocks": (I, [P]),
     "cris_ema_advance": (I, [P, I, F, I, P, P]),
     "cris_ema_update": (I, [P, I, I, P, P]),
+    "cris_adam_schedule_lrs": (I, [P, I, P, P, P, I, I, P, P]),
     "cris_p2p_mailbox_bytes": (C.c_size_t, [I, I, I]),
     "cris_p2p_alloc": (I, [C.c_size_t, P]),
     "cris_p2p_free": (I, [P]),

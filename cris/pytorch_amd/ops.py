@@ -1146,6 +1146,63 @@ class EmaTable:
         hip.call("cris_ema_update", ptr(self.dev), len(self.named), self.total_blocks, ptr(self.state), _stream())
 
 
+class LrSchedule:
+    """Per-step learning rates of an AdamTable, followed on the device: a float32 table [n_rows, n_groups] (row t = the rates of
+    0-based optimizer step t, steps past the end use the last row), one uint8 group index per descriptor of either Adam table
+    (ordered by AdamTable.index[taps]) and lr_out [n_groups], the rates the last applied step used.  All three keep their
+    addresses for the schedule's lifetime (graph replay).  apply() is one launch per non-empty Adam table."""
+
+    @staticmethod
+    def checked_table(table, n_groups=None):
+        """`table` as a C-contiguous float32 numpy array [n_rows, n_groups], or ValueError: 2-d, n_rows >= 1, 1 <= n_groups <= 255
+        (== n_groups when given), every value finite and >= 0.  Converted to float32 once, here."""
+        import numpy as np
+        try:
+            a = np.ascontiguousarray(np.asarray(table, dtype=np.float32))
+        except (TypeError, ValueError) as ex:
+            raise ValueError("lr table must be an array of numbers: %s" % ex)
+        if a.ndim != 2:
+            raise ValueError("lr table must be 2-d [n_rows, n_groups], got shape %r" % (a.shape,))
+        if a.shape[0] < 1:
+            raise ValueError("lr table needs at least one row, got shape %r" % (a.shape,))
+        if not 1 <= a.shape[1] <= 255 or (n_groups is not None and a.shape[1] != n_groups):
+            raise ValueError("lr table must have %s columns (one per group), got shape %r"
+                             % ("1 to 255" if n_groups is None else n_groups, a.shape))
+        if not bool(np.isfinite(a).all()) or bool((a < 0).any()):
+            raise ValueError("lr table values must be finite and >= 0")
+        return a
+
+    def __init__(self, adam, group_of, table, checked=False):
+        """adam: the AdamTable whose rates are scheduled; group_of[i]: the column of tensor i (AdamTable's order); table: see
+        checked_table (checked=True: it is that function's result already and is taken as it is).  Everything is validated
+        before a device is touched."""
+        self.table = table if checked else self.checked_table(table)
+        self.n_rows, self.n_groups = self.table.shape
+        group_of = [int(g) for g in group_of]
+        if any(not 0 <= g < self.n_groups for g in group_of):
+            raise ValueError("group index outside the lr table's %d columns" % self.n_groups)
+        if len(group_of) != len(adam.params):
+            raise ValueError("%d group indices for %d tensors" % (len(group_of), len(adam.params)))
+        self.adam, self.device = adam, adam.device
+        self.table_dev = torch.from_numpy(self.table).to(self.device)
+        self.group_dev = {taps: torch.tensor([group_of[i] for i in idx], dtype=torch.uint8).to(self.device)
+                          for taps, idx in adam.index.items() if idx}
+        self.lr_out = torch.zeros(self.n_groups, dtype=torch.float32, device=self.device)
+
+    def at(self, step):
+        """host mirror of the kernel's row choice: the rates (float32 [n_groups]) 0-based optimizer step `step` uses"""
+        return self.table[min(max(int(step), 0), self.n_rows - 1)].copy()
+
+    def apply(self, step_dev):
+        """write the rates of step step_dev[0] (1-based: the counter has been advanced) into both Adam tables and into lr_out.
+        The tables' addresses are taken now: AdamTable.set_lrs uploads them to new ones."""
+        for taps in (9, 1):
+            t = self.adam.tables[taps]
+            if t.n:
+                hip.call("cris_adam_schedule_lrs", ptr(t.dev), t.n, ptr(self.group_dev[taps]), ptr(step_dev), ptr(self.table_dev),
+                         self.n_rows, self.n_groups, ptr(self.lr_out), _stream())
+
+
 class UnpackTable:
     """Device table for cris_unpack_grads: GEMM-layout gradients (srcs) -> parameter-layout tensors (dsts)."""
 

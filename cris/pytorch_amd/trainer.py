@@ -32,6 +32,13 @@ captured / recorded step: `cris_ema_advance` decides on the device whether this 
 with which weight (`ema_warmup`), `cris_ema_update` applies ema += (p - ema) * weight to everything.  Once per optimizer step,
 not per micro-batch; no communication (parameters, hence averages, are identical on every rank).  ema_state_dict() has the keys
 of model_state_dict().  With ema_decay=None (the default) nothing is allocated and the step issues the launches it always did.
+
+Per-step learning rates (`lr_schedule=table`): a float32 table [n_steps, 2] - row t = (backbone rate, rate of the rest) of 0-based
+optimizer step t, steps past the end use the last row - lives on the device (ops.LrSchedule).  Immediately before the Adam launches
+`cris_adam_schedule_lrs` (one launch per Adam table) copies the row of the running step, chosen from the device step counter, into
+the `lr` fields of the Adam descriptors, where the Adam kernels read it: warm-up, cosine, one-cycle or any other per-iteration
+schedule (cris.pytorch_amd.lr builds the tables) without host work and without a new capture.  Once per optimizer step, no
+communication (every rank passes the same table).  With lr_schedule=None (the default) the step issues the launches it always did.
 """
 import contextlib
 import os
@@ -77,8 +84,10 @@ class NativeTrainer:
     def __init__(self, clip: ClipSpec, head: HeadSpec, state_dict, device, base_lr=1e-4, lr_multi=0.1, weight_decay=0.0,
                  comm=None, sync_bn=False, use_graph: Optional[bool] = None, launch: Optional[str] = None, max_norm: float = 0.0,
                  track_grad_norm: bool = False, accum_steps: int = 1, ema_decay: Optional[float] = None, ema_every: int = 1,
-                 ema_warmup: bool = False):
-        """ema_decay = d in (0, 1): keep an exponential moving average of parameters and BatchNorm statistics, updated every
+                 ema_warmup: bool = False, lr_schedule=None):
+        """lr_schedule = array-like [n_steps, 2]: the (backbone, rest) learning rates of every optimizer step, followed on the device
+        inside the captured step (the module docstring; set_lr_schedule; cris.pytorch_amd.lr builds such tables).
+        ema_decay = d in (0, 1): keep an exponential moving average of parameters and BatchNorm statistics, updated every
         `ema_every`-th optimizer step with weight 1 - d (ema_warmup: 1 - min(d, (1 + t) / (10 + t)) for update t); set_ema.
         accum_steps = K > 1: one train_step is one optimizer step over K micro-batches (the module docstring; set_accum_steps).
         max_norm > 0: clip the gradients by their global 2-norm like the reference's `clip_grad_norm_(model.parameters(),
@@ -89,6 +98,7 @@ class NativeTrainer:
         self.max_norm, self.track_grad_norm = float(max_norm), bool(track_grad_norm)
         self.accum_steps = self._checked_accum(accum_steps)
         ema_cfg = self._checked_ema(ema_decay, ema_every, ema_warmup)
+        lr_schedule = self._checked_schedule(lr_schedule)
         self.device = device
         params, buffers = split_state_dict(state_dict, device)
         self.engine = Engine(clip, head, params, buffers, device, comm=comm, sync_bn=sync_bn)
@@ -172,6 +182,8 @@ class NativeTrainer:
         self.set_accum_steps(self.accum_steps)
         self._ema = None
         self.set_ema(*ema_cfg)                   # (after the rank-0 broadcast above: the average starts from the shared values)
+        self._lr = None
+        self.set_lr_schedule(lr_schedule)
         self._peer_check_every = int(os.environ.get("CRIS_PEER_CHECK_EVERY", "200"))
 
     def _build_adam(self, lrs):
@@ -192,6 +204,9 @@ class NativeTrainer:
         return int(self.step_dev.item())
 
     def set_group_lrs(self, lr_backbone, lr_head):
+        """learning rates of the two groups from now on (host write + upload of the Adam tables; the step is captured / recorded
+        again).  While a per-step schedule is on (set_lr_schedule) they last only until the next step, which overwrites them with
+        its row of the table."""
         lrs = [lr_backbone if self.group[n] == 0 else lr_head for n in self.names]
         self.adam.set_lrs(lrs)
         self._graph = self._cmds = None          # learning rates live in the device table, which was re-uploaded (new
@@ -251,6 +266,43 @@ class NativeTrainer:
         self._graph = self._cmds = None
         self._eager_steps = 0
 
+    @staticmethod
+    def _checked_schedule(table):
+        """None, or the table as float32 numpy [n_steps, 2] (converted once); ValueError for anything else"""
+        if table is None:
+            return None
+        try:
+            return ops.LrSchedule.checked_table(table, n_groups=2)
+        except ValueError as ex:
+            raise ValueError("lr_schedule: %s" % ex)
+
+    def set_lr_schedule(self, table):
+        """switch the per-step learning rates on or replace them (array-like [n_steps, 2]: column 0 the backbone group, column 1
+        the rest; row t = the rates of 0-based optimizer step t, steps past the end use the last row), or switch them off (None:
+        the device buffers are freed and the rates set last through set_group_lrs / set_epoch / the constructor hold again).  The
+        step is captured / recorded again.  The row is chosen from the optimizer step count, which load_optimizer_state_dict
+        restores: a resumed run continues at the right row once the same table has been set; the table itself is configuration
+        and not part of optimizer_state_dict().  As with torch, a state saved under a schedule carries the next row's rates as the
+        groups' `lr`, and load_optimizer_state_dict makes them the host's rates (set_group_lrs): on a resumed trainer those, not
+        the constructor's, are what None goes back to - call set_group_lrs / set_epoch after switching off to choose others."""
+        table = self._checked_schedule(table)
+        if table is None:
+            if self._lr is not None:
+                self._lr = None
+                self.adam.set_lrs(self.adam.lrs)         # the device tables hold the last row: back to the host's rates
+        else:
+            self._lr = ops.LrSchedule(self.adam, [self.group[n] for n in self.names], table, checked=True)
+        self._graph = self._cmds = None
+        self._eager_steps = 0
+
+    @property
+    def current_lrs(self):
+        """(backbone rate, rate of the rest) the last step used: a device tensor [2] written by the step itself (no sync here),
+        overwritten by the next step; zeros before the first one.  Only with a per-step schedule."""
+        if self._lr is None:
+            raise RuntimeError("current_lrs is written only with a per-step schedule: pass lr_schedule or call set_lr_schedule(table)")
+        return self._lr.lr_out
+
     def _ema_table(self):
         if self._ema is None:
             raise RuntimeError("no weight average is kept: build the trainer with ema_decay or call set_ema(decay)")
@@ -270,7 +322,9 @@ class NativeTrainer:
         return self.adam.gnorm[0]
 
     def set_epoch(self, epoch, milestones=(35,), gamma=0.1):
-        """Learning rates of the reference schedule for `epoch` (0-based); call at every epoch boundary."""
+        """Learning rates of the reference schedule for `epoch` (0-based); call at every epoch boundary.  While a per-step schedule
+        is on (set_lr_schedule) the next step overwrites them with its row of the table: use one or the other
+        (lr.reference_epochs is this recipe as a table)."""
         self.set_group_lrs(*epoch_group_lrs(epoch, self.base_lr, self.lr_multi, milestones, gamma))
 
     # ------------------------------------------------------------------------------------------------
@@ -313,6 +367,8 @@ class NativeTrainer:
             gn = self.adam.grad_norm(grad_scale=1.0 / self.comm.world, max_norm=self.max_norm if self.max_norm > 0 else None)
             if self.max_norm > 0:
                 divisor = gn[1:2]
+        if self._lr is not None:
+            self._lr.apply(self.step_dev)
         self.adam.step(weight_decay=self.weight_decay, grad_scale=1.0 / self.comm.world, step_dev=self.step_dev, loss_scale_dev=divisor)
         e.packs_current = self.adam.refreshes_packs
         if self._ema is not None:
@@ -367,6 +423,8 @@ class NativeTrainer:
             gn = self.adam.grad_norm(grad_scale=scale, max_norm=self.max_norm if self.max_norm > 0 else None)
             if self.max_norm > 0:
                 divisor = gn[1:2]
+        if self._lr is not None:                 # once per optimizer step: the row of step_dev, which micro-batch 0 advanced
+            self._lr.apply(self.step_dev)
         self.adam.step(weight_decay=self.weight_decay, grad_scale=scale, step_dev=self.step_dev, loss_scale_dev=divisor)
         e.packs_current = self.adam.refreshes_packs
         if self._ema is not None:                # once per optimizer step, after the K-th micro-batch's update
@@ -510,11 +568,15 @@ class NativeTrainer:
 
     def optimizer_state_dict(self):
         """Adam state in torch.optim.Adam.state_dict() form, loadable by the optimizer `train.py:105-107` builds from
-        `build_segmenter`'s param_list (and by load_optimizer_state_dict)."""
+        `build_segmenter`'s param_list (and by load_optimizer_state_dict).  With a per-step schedule the groups' `lr` is the row
+        the NEXT step will use (as torch reports it after scheduler.step()); the table itself is not saved."""
         g0, g1 = self._param_order()
         idx = {n: i for i, n in enumerate(self.names)}
         lr_of = dict(zip(self.names, self.adam.lrs))
         state, step = {}, self.step_idx
+        if self._lr is not None:
+            row = [float(x) for x in self._lr.at(step)]
+            lr_of = {n: row[self.group[n]] for n in self.names}
         for i, n in enumerate(g0 + g1):
             if n in idx and step > 0:
                 j = idx[n]
@@ -528,7 +590,8 @@ class NativeTrainer:
 
     def load_optimizer_state_dict(self, sd):
         """restore m / v / step count (and the group learning rates) from optimizer_state_dict() or from the state_dict of a
-        torch.optim.Adam over the same param_list"""
+        torch.optim.Adam over the same param_list.  The groups' `lr` become the host's rates through set_group_lrs; a state saved
+        under a per-step schedule holds a row of its table there (set_lr_schedule)."""
         g0, g1 = self._param_order()
         idx = {n: i for i, n in enumerate(self.names)}
         step = 0

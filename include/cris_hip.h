@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -617,6 +617,18 @@ typedef struct {
 int cris_ema_blocks(const cris_ema_desc* d);
 int cris_ema_advance(const int32_t* step_dev, int every, float decay, int warmup, void* state, void* stream);
 int cris_ema_update(const cris_ema_desc* dev_table, int n_desc, int total_blocks, const void* state, void* stream);
+
+/* Per-step learning-rate schedule inside the step (csrc/lr.hip), launched once per Adam table before cris_adam_step[_amp]:
+ *   s = step_dev[0], the 1-based optimizer step cris_step_advance[_micro] already advanced; row = min(max(s - 1, 0), n_rows - 1);
+ *   dev_table[i].lr = lr_table[row * n_groups + group_of[i]] for i < n_desc (one plain float store per thread: no other byte of a
+ *   descriptor changes); lr_out (optional) [g] = lr_table[row * n_groups + g] for g < n_groups.
+ * Values are copied, never computed, so the table's schedule is followed bit for bit.  256 threads per block, ceil(n_desc / 256)
+ * blocks.  Non-zero with cris_last_error() before anything is launched: a null dev_table, group_of, step_dev or lr_table;
+ * n_desc < 1; n_rows < 1; n_groups outside [1, 255].  Every group_of[i] must be < n_groups (the caller checks; a larger one leaves
+ * its descriptor unchanged). */
+int cris_adam_schedule_lrs(cris_adam_desc* dev_table, int n_desc, const uint8_t* group_of /*[n_desc], device*/,
+                           const int32_t* step_dev, const float* lr_table /*[n_rows][n_groups], device*/,
+                           int n_rows, int n_groups, float* lr_out /*[n_groups], device, may be NULL*/, void* stream);
 
 /* ---- The sentence-vector path in fp32 (csrc/smallf32.hip) ----------------------------------------------------------------
  * At most CRIS_SMALL_MAX_ROWS (= the per-GPU batch) rows: LayerNorm of the end-of-text rows (model/clip.py:449-452), `@
