@@ -80,6 +80,17 @@ def epoch_group_lrs(epoch, base_lr, lr_multi, milestones, gamma):
     return lr_multi * base_lr * f, base_lr * f
 
 
+def in_backbone_group(name):
+    """`build_segmenter`'s name rule (model/__init__.py:36-48): group 0 = backbone without the positional embeddings, group 1 = the rest"""
+    return name.startswith("backbone") and "positional_embedding" not in name
+
+
+def checked_int(what, value, lowest):
+    if isinstance(value, bool) or not isinstance(value, int) or value < lowest:
+        raise ValueError("%s must be an integer >= %d, got %r" % (what, lowest, value))
+    return value
+
+
 class NativeTrainer:
     def __init__(self, clip: ClipSpec, head: HeadSpec, state_dict, device, base_lr=1e-4, lr_multi=0.1, weight_decay=0.0,
                  comm=None, sync_bn=False, use_graph: Optional[bool] = None, launch: Optional[str] = None, max_norm: float = 0.0,
@@ -93,10 +104,8 @@ class NativeTrainer:
         max_norm > 0: clip the gradients by their global 2-norm like the reference's `clip_grad_norm_(model.parameters(),
         args.max_norm)` (engine/engine.py:54-55); 0 (the shipped configs): no clipping.  track_grad_norm: compute `grad_norm`
         every step without clipping."""
-        if not max_norm >= 0:
-            raise ValueError("max_norm must be >= 0 (0 = no clipping), got %r" % (max_norm,))
-        self.max_norm, self.track_grad_norm = float(max_norm), bool(track_grad_norm)
-        self.accum_steps = self._checked_accum(accum_steps)
+        self.max_norm, self.track_grad_norm = self._checked_max_norm(max_norm), bool(track_grad_norm)
+        self.accum_steps = checked_int("accum_steps", accum_steps, 1)
         ema_cfg = self._checked_ema(ema_decay, ema_every, ema_warmup)
         lr_schedule = self._checked_schedule(lr_schedule)
         self.device = device
@@ -114,7 +123,7 @@ class NativeTrainer:
         # lr=base_lr and groups that only carry `initial_lr`, so BOTH groups start at base_lr.
         names = [n for n in e.grad_order if n != "backbone.logit_scale"]          # never receives a gradient (unused)
         self.names = names
-        self.group = {n: (0 if (n.startswith("backbone") and "positional_embedding" not in n) else 1) for n in names}
+        self.group = {n: (0 if in_backbone_group(n) else 1) for n in names}
         self.base_lr, self.lr_multi, self.weight_decay = base_lr, lr_multi, weight_decay
         # Rows of the token embedding (49408 x 512: 17% of the parameters) that have never received a gradient keep g = m = v = 0
         # and Adam leaves them exactly as they are (while weight_decay == 0): the embedding backward marks the rows of each
@@ -172,10 +181,8 @@ class NativeTrainer:
         assert launch in ("graph", "cmdlist", "eager"), launch
         self.launch = launch
         self.use_graph = launch != "eager"
-        self._graph = None
-        self._cmds = None
+        self._invalidate()
         self._static = None
-        self._eager_steps = 0
         self.graph_error = None
         self._host_steps = 0
         self._acc = self._loss_acc = self._metric_micro = None
@@ -209,28 +216,30 @@ class NativeTrainer:
         its row of the table."""
         lrs = [lr_backbone if self.group[n] == 0 else lr_head for n in self.names]
         self.adam.set_lrs(lrs)
-        self._graph = self._cmds = None          # learning rates live in the device table, which was re-uploaded (new
-        self._eager_steps = 0                    # address): capture / record again
+        self._invalidate()                       # learning rates live in the device table, which was re-uploaded (new address)
 
     def set_max_norm(self, max_norm):
         """change the clipping threshold (0 = off); it is an argument of a launch, so the step is captured / recorded again"""
-        if not max_norm >= 0:
-            raise ValueError("max_norm must be >= 0 (0 = no clipping), got %r" % (max_norm,))
-        self.max_norm = float(max_norm)
-        self._graph = self._cmds = None
-        self._eager_steps = 0
+        self.max_norm = self._checked_max_norm(max_norm)
+        self._invalidate()
 
     @staticmethod
-    def _checked_accum(k):
-        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
-            raise ValueError("accum_steps must be an integer >= 1, got %r" % (k,))
-        return k
+    def _checked_max_norm(max_norm):
+        if not max_norm >= 0:
+            raise ValueError("max_norm must be >= 0 (0 = no clipping), got %r" % (max_norm,))
+        return float(max_norm)
+
+    def _invalidate(self):
+        """the captured graph / recorded list no longer describes the step: the next one runs eagerly, the one after it captures
+        or records again"""
+        self._graph = self._cmds = None
+        self._eager_steps = 0
 
     def set_accum_steps(self, accum_steps):
         """number of micro-batches per optimizer step; the step is captured / recorded again.  K > 1 holds a second buffer of the
         gradient arena's size (the running sum), K == 1 holds none and runs exactly the step of a trainer without accumulation.
         The dropout seeds follow (step * K + micro) * 7919 + 17 with the K of the running step."""
-        self.accum_steps = self._checked_accum(accum_steps)
+        self.accum_steps = checked_int("accum_steps", accum_steps, 1)
         if self.accum_steps > 1:
             if self._acc is None:
                 self._acc = torch.empty_like(self.engine.grad_arena)
@@ -238,16 +247,13 @@ class NativeTrainer:
                 self._metric_micro = torch.zeros(2, device=self.device)
         else:
             self._acc = self._loss_acc = self._metric_micro = None
-        self._graph = self._cmds = None
-        self._eager_steps = 0
+        self._invalidate()
 
     @staticmethod
     def _checked_ema(decay, every, warmup):
         if decay is not None and (isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 < decay < 1.0):
             raise ValueError("ema_decay must be None (off) or a number in (0, 1), got %r" % (decay,))
-        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
-            raise ValueError("ema_every must be an integer >= 1, got %r" % (every,))
-        return (None if decay is None else float(decay)), every, bool(warmup)
+        return (None if decay is None else float(decay)), checked_int("ema_every", every, 1), bool(warmup)
 
     def set_ema(self, decay, every=1, warmup=False):
         """switch the weight average on (0 < decay < 1), change its settings, or switch it off (None: the buffer is freed); the
@@ -263,8 +269,7 @@ class NativeTrainer:
             self._ema = ops.EmaTable(list(e.P.items()) + list(e.Bf.items()),
                                      row_live={name: e.embed_live} if e.embed_live is not None else None)
             self._ema.reset()
-        self._graph = self._cmds = None
-        self._eager_steps = 0
+        self._invalidate()
 
     @staticmethod
     def _checked_schedule(table):
@@ -292,8 +297,7 @@ class NativeTrainer:
                 self.adam.set_lrs(self.adam.lrs)         # the device tables hold the last row: back to the host's rates
         else:
             self._lr = ops.LrSchedule(self.adam, [self.group[n] for n in self.names], table, checked=True)
-        self._graph = self._cmds = None
-        self._eager_steps = 0
+        self._invalidate()
 
     @property
     def current_lrs(self):
@@ -329,107 +333,94 @@ class NativeTrainer:
 
     # ------------------------------------------------------------------------------------------------
     def _step_body(self, img, word, mask, host_seed: Optional[int]):
-        e = self.engine
-        if self.accum_steps > 1:
-            return self._step_body_accum(img, word, mask, host_seed)
-        if host_seed is None:
-            ops.step_advance(self.step_dev, self.seed_dev, self.xgen_dev)
-            e.seed_dev, seed = self.seed_dev, 0
-        else:                                    # explicit seed (tests): host value, the device counter still advances
-            ops.step_advance(self.step_dev, self.seed_dev, self.xgen_dev)
-            e.seed_dev, seed = None, host_seed
-        pred, msk, loss = e.forward(img, word, mask, training=True, seed=seed)
-        # the train metric (utils/misc.py:114-129) only needs the logits: it runs on the text-encoder stream underneath the
-        # backward pass (backward() joins that stream before it returns)
+        """the step over K = accum_steps micro-batches (views of the inputs' K equal slices; the module docstring).  K == 1 is the
+        plain step: no running sums, the metric written straight into self.metric, the engine's own loss returned"""
+        e, K = self.engine, self.accum_steps
+        b = img.shape[0] // K
+        if K > 1:
+            ops.zero_(self._loss_acc)
+            ops.zero_(self.metric)
+        for m in range(K):
+            if K == 1:
+                ops.step_advance(self.step_dev, self.seed_dev, self.xgen_dev)
+            else:
+                # the step counter advances with micro-batch 0, the seed and the mailbox generation with every micro-batch
+                ops.step_advance_micro(self.step_dev, self.seed_dev, self.xgen_dev, m, K)
+            if host_seed is None:
+                e.seed_dev, seed = self.seed_dev, 0
+            else:                                # explicit seed (tests): a host value, seed + m for micro-batch m; the device
+                e.seed_dev, seed = None, host_seed + m                                        # counter still advances
+            micro = (img, word, mask) if K == 1 else [x[m * b:(m + 1) * b] for x in (img, word, mask)]
+            pred, msk, loss = e.forward(*micro, training=True, seed=seed)
+            if K > 1:
+                ops.axpy_f32(self._loss_acc, loss, 1.0 / K)
+            self._metric(pred, msk)
+            e.backward(on_stage_done=self._stage_hook(m))
+        if self._exchanges():
+            ops.torch_op(self.comm.wait_all)
+        self._update(1.0 / (self.comm.world * K))            # the 1/K goes where 1/world goes
+        return (loss if K == 1 else self._loss_acc), pred, msk
+
+    def _exchanges(self):
+        return self.comm.world > 1 or debug.HOOKS.force_dist
+
+    def _metric(self, pred, msk):
+        """the train metric (utils/misc.py:114-129) only needs the logits: it runs on the text-encoder stream underneath the
+        backward pass (backward() joins that stream before it returns).  K > 1: the mean of the micro-batches' metrics, which is
+        the whole batch's (equal sizes)"""
+        e, K = self.engine, self.accum_steps
         if e.side is not None:
             cur = torch.cuda.current_stream()
             ops.torch_op(lambda: e.side.wait_stream(cur))
-            with torch.cuda.stream(e.side):
-                ops.train_metric(pred, msk, pred.shape[0], pred.shape[2] * pred.shape[3], self.metric)
-        else:
-            ops.train_metric(pred, msk, pred.shape[0], pred.shape[2] * pred.shape[3], self.metric)
-        if self.comm.world > 1 or debug.HOOKS.force_dist:
-            def on_stage(st):
-                lo, hi = e.stage_ranges[st]
-                ops.torch_op(lambda: self.comm.allreduce_async(e.grad_arena[lo:hi]))
-                if st == 4 and e.embed_live is not None and getattr(self.comm, "supports_max_u8", False):
-                    # (stage 4 = the text encoder, whose backward marked this batch's rows of the token embedding)
-                    ops.torch_op(lambda: self.comm.allreduce_async(e.embed_live, op="max"))
-            e.backward(on_stage_done=on_stage)
-            ops.torch_op(self.comm.wait_all)
-        else:
-            e.backward()
-        # one Adam pass over every tensor; it also rewrites the bf16 operand copies of the GEMM weights from the new values
-        divisor = None
-        if self.max_norm > 0 or self.track_grad_norm:
-            # clip_grad_norm_ (engine/engine.py:54-55) as a divisor of the update: the norm of the averaged gradient and
-            # max(1, norm / max_norm) are left on the device, the Adam kernels divide by it where GradScaler's scale goes
-            gn = self.adam.grad_norm(grad_scale=1.0 / self.comm.world, max_norm=self.max_norm if self.max_norm > 0 else None)
-            if self.max_norm > 0:
-                divisor = gn[1:2]
-        if self._lr is not None:
-            self._lr.apply(self.step_dev)
-        self.adam.step(weight_decay=self.weight_decay, grad_scale=1.0 / self.comm.world, step_dev=self.step_dev, loss_scale_dev=divisor)
-        e.packs_current = self.adam.refreshes_packs
-        if self._ema is not None:
-            self._ema.update(self.step_dev, self.ema_every, self.ema_decay, self.ema_warmup)
-        return loss, pred, msk
-
-    def _step_body_accum(self, img, word, mask, host_seed: Optional[int]):
-        """the step over K = accum_steps micro-batches (views of the inputs' K equal slices); see the module docstring"""
-        e, K = self.engine, self.accum_steps
-        b = img.shape[0] // K
-        exchange = self.comm.world > 1 or debug.HOOKS.force_dist
-        ops.zero_(self._loss_acc)
-        ops.zero_(self.metric)
-        for m in range(K):
-            last = m == K - 1
-            # the step counter advances with micro-batch 0, the seed and the mailbox generation with every micro-batch
-            ops.step_advance_micro(self.step_dev, self.seed_dev, self.xgen_dev, m, K)
-            if host_seed is None:
-                e.seed_dev, seed = self.seed_dev, 0
-            else:                                # explicit seed (tests): seed + m for micro-batch m
-                e.seed_dev, seed = None, host_seed + m
-            sl = slice(m * b, (m + 1) * b)
-            pred, msk, loss = e.forward(img[sl], word[sl], mask[sl], training=True, seed=seed)
-            ops.axpy_f32(self._loss_acc, loss, 1.0 / K)
-            # mean of the micro-batches' metrics = the whole batch's (equal sizes); on the text-encoder stream like the K = 1 step
-            if e.side is not None:
-                cur = torch.cuda.current_stream()
-                ops.torch_op(lambda: e.side.wait_stream(cur))
-            with (torch.cuda.stream(e.side) if e.side is not None else contextlib.nullcontext()):
-                ops.train_metric(pred, msk, pred.shape[0], pred.shape[2] * pred.shape[3], self._metric_micro)
+        with (torch.cuda.stream(e.side) if e.side is not None else contextlib.nullcontext()):
+            ops.train_metric(pred, msk, pred.shape[0], pred.shape[2] * pred.shape[3], self.metric if K == 1 else self._metric_micro)
+            if K > 1:
                 ops.axpy_f32(self.metric, self._metric_micro, 1.0 / K)
 
-            def on_stage(st, m=m, last=last):
-                # fires on the stream the stage's gradients were issued on (stage 4: the side stream)
-                lo, hi = e.stage_ranges[st]
-                g, acc = e.grad_arena[lo:hi], self._acc[lo:hi]
+    def _stage_hook(self, m):
+        """backward's stage hook of micro-batch m, or None when there is neither a sum to keep nor an exchange to start.  It fires on
+        the stream the stage's gradients were issued on (stage 4: the side stream)"""
+        e, K, exchange = self.engine, self.accum_steps, self._exchanges()
+        if K == 1 and not exchange:
+            return None
+        last = m == K - 1
+
+        def on_stage(st):
+            lo, hi = e.stage_ranges[st]
+            g = e.grad_arena[lo:hi]
+            if K > 1:
+                acc = self._acc[lo:hi]
                 if not last:
                     ops.grad_accumulate(acc, g, add=m > 0)       # acc = g0 ; acc += g_m
                     return
                 ops.grad_accumulate(g, acc)                      # the total, in the arena, before the stage's exchange
-                if exchange:
-                    ops.torch_op(lambda: self.comm.allreduce_async(g))
-                    if st == 4 and e.embed_live is not None and getattr(self.comm, "supports_max_u8", False):
-                        # (sticky marks: the rows of every micro-batch of this step, and of every step before)
-                        ops.torch_op(lambda: self.comm.allreduce_async(e.embed_live, op="max"))
-            e.backward(on_stage_done=on_stage)
-        if exchange:
-            ops.torch_op(self.comm.wait_all)
-        scale = 1.0 / (self.comm.world * K)
+            if exchange:
+                self._exchange_stage(st, g)
+        return on_stage
+
+    def _exchange_stage(self, st, g):
+        ops.torch_op(lambda: self.comm.allreduce_async(g))
+        if st == 4 and self.engine.embed_live is not None and getattr(self.comm, "supports_max_u8", False):
+            # (stage 4 = the text encoder, whose backward marked the rows of the token embedding; the marks are sticky: the rows
+            # of every micro-batch of this step, and of every step before)
+            ops.torch_op(lambda: self.comm.allreduce_async(self.engine.embed_live, op="max"))
+
+    def _update(self, grad_scale):
+        """the tail of the step, once per optimizer step: norm / divisor, schedule row, one Adam pass over every tensor (it also
+        rewrites the bf16 operand copies of the GEMM weights from the new values), EMA"""
         divisor = None
         if self.max_norm > 0 or self.track_grad_norm:
-            gn = self.adam.grad_norm(grad_scale=scale, max_norm=self.max_norm if self.max_norm > 0 else None)
+            # clip_grad_norm_ (engine/engine.py:54-55) as a divisor of the update: the norm of the averaged gradient and
+            # max(1, norm / max_norm) are left on the device, the Adam kernels divide by it where GradScaler's scale goes
+            gn = self.adam.grad_norm(grad_scale=grad_scale, max_norm=self.max_norm if self.max_norm > 0 else None)
             if self.max_norm > 0:
                 divisor = gn[1:2]
-        if self._lr is not None:                 # once per optimizer step: the row of step_dev, which micro-batch 0 advanced
+        if self._lr is not None:                 # the row of step_dev, which micro-batch 0 advanced
             self._lr.apply(self.step_dev)
-        self.adam.step(weight_decay=self.weight_decay, grad_scale=scale, step_dev=self.step_dev, loss_scale_dev=divisor)
-        e.packs_current = self.adam.refreshes_packs
-        if self._ema is not None:                # once per optimizer step, after the K-th micro-batch's update
+        self.adam.step(weight_decay=self.weight_decay, grad_scale=grad_scale, step_dev=self.step_dev, loss_scale_dev=divisor)
+        self.engine.packs_current = self.adam.refreshes_packs
+        if self._ema is not None:
             self._ema.update(self.step_dev, self.ema_every, self.ema_decay, self.ema_warmup)
-        return self._loss_acc, pred, msk
 
     def train_step(self, img, word, mask, seed: Optional[int] = None):
         """One optimizer step.  Returns (loss 0-dim device tensor, metric [IoU%, Pr@50%] device tensor); both are
@@ -448,7 +439,8 @@ class NativeTrainer:
             return loss, self.metric
         key = (tuple(img.shape), tuple(word.shape), tuple(mask.shape))
         if self._static is not None and self._static[0] != key:
-            self._graph, self._cmds, self._static, self._eager_steps = None, None, None, 0      # new shapes: new schedule
+            self._invalidate()                   # new shapes: new schedule
+            self._static = None
         self._static = (key, capture.stage(self._static and self._static[1], (img, word, mask), self.device))
         if self._graph is None and self._cmds is None:
             def body():
@@ -498,9 +490,7 @@ class NativeTrainer:
         (model/__init__.py:36-48): group 0 = backbone without the positional embeddings, group 1 = the rest - module order
         inside each group.  `backbone.logit_scale` is a parameter of the reference module too (it just never gets a gradient)."""
         names = list(self.engine.P.keys())                    # state_dict (= named_parameters) order
-        g0 = [n for n in names if n.startswith("backbone") and "positional_embedding" not in n]
-        g1 = [n for n in names if n not in set(g0)]
-        return g0, g1
+        return [n for n in names if in_backbone_group(n)], [n for n in names if not in_backbone_group(n)]
 
     def model_state_dict(self, ddp_prefix=False):
         """the reference module's `state_dict()` (parameters + BatchNorm buffers; clones, on the CPU).  `ddp_prefix=True`:
@@ -531,16 +521,20 @@ class NativeTrainer:
             out = {"module." + k: v for k, v in out.items()}
         return out
 
+    def _load_named(self, targets, sd):
+        """copy sd[name] into every tensor of `targets` {name: tensor}; sd's keys may all carry DDP's `module.` prefix"""
+        sd = strip_ddp_prefix(sd)
+        missing = [k for k in targets if k not in sd]
+        if missing:
+            raise KeyError("state_dict lacks %d keys, e.g. %s" % (len(missing), missing[:3]))
+        for k, t in targets.items():
+            t.copy_(sd[k].to(self.device))
+
     def load_model_state_dict(self, sd):
         """parameters and BatchNorm buffers from a reference-keyed state_dict; the bf16 operand copies are re-packed on the
         next forward.  Keys may carry DDP's `module.` prefix (reference checkpoints do)."""
         e = self.engine
-        sd = strip_ddp_prefix(sd)
-        missing = [k for k in list(e.P) + list(e.Bf) if k not in sd]
-        if missing:
-            raise KeyError("state_dict lacks %d keys, e.g. %s" % (len(missing), missing[:3]))
-        for k, t in list(e.P.items()) + list(e.Bf.items()):
-            t.copy_(sd[k].to(self.device))
+        self._load_named({**e.P, **e.Bf}, sd)
         e.packs_current = False
         if self._ema is not None:                # the average restarts from the loaded weights (load_ema_state_dict overrides)
             self._ema.reset()
@@ -549,14 +543,8 @@ class NativeTrainer:
         """restore the averaged weights (ema_state_dict(); keys may carry `module.`) and the update count (ema_num_updates).
         When resuming, call it after load_model_state_dict, which resets the average to the loaded weights."""
         ema, e = self._ema_table(), self.engine
-        if isinstance(num_updates, bool) or not isinstance(num_updates, int) or num_updates < 0:
-            raise ValueError("num_updates must be an integer >= 0, got %r" % (num_updates,))
-        sd = strip_ddp_prefix(sd)
-        missing = [k for k in ema.views if k not in sd]
-        if missing:
-            raise KeyError("state_dict lacks %d keys, e.g. %s" % (len(missing), missing[:3]))
-        for k, v in ema.views.items():
-            v.copy_(sd[k].to(self.device))
+        checked_int("num_updates", num_updates, 0)
+        self._load_named(ema.views, sd)
         ema.state.copy_(torch.tensor([num_updates, 0, 0, 0], dtype=torch.int32))
         # the update skips embedding rows that never had a gradient because there ema == p; an average from elsewhere may differ
         # from the parameters in such a row, and the skip would freeze that difference: then every row is updated from now on

@@ -9,12 +9,11 @@ from conftest import ROOT  # noqa: F401  (puts the repository root on sys.path)
 
 pytestmark = pytest.mark.gpu
 
-from cris.pytorch_amd import arch, hip, ops, synth  # noqa: E402
+from cris.pytorch_amd import arch, hip, ops  # noqa: E402
 from cris.pytorch_amd.infer import InferenceRunner  # noqa: E402
-from cris.pytorch_amd.trainer import NativeTrainer  # noqa: E402
+from trainer_cases import MICRO, batch, make_trainer, recorded, same_floats  # noqa: E402
 
 DEV = "cuda"
-MICRO = 2
 EMBED = "backbone.token_embedding.weight"
 SENTINEL = 12345.0
 
@@ -125,15 +124,6 @@ def test_kernel_equals_the_torch_formula_bit_for_bit():
 
 
 # ---- the trainer ------------------------------------------------------------------------------------------------------
-def make_trainer(**kw):
-    clip, head = arch.specs_by_name("tiny")
-    return NativeTrainer(clip, head, arch.synthetic_state_dict(clip, head, 0), torch.device("cuda:0"), **kw), head
-
-
-def batch(n, head, t):
-    return [x.to("cuda:0") for x in synth.make_batch(n, 64, head.word_len, 0, t)]
-
-
 def train(tr, head, first, steps, out=None):
     out = out if out is not None else dict(losses=[], metrics=[], snaps=[])
     for t in range(first, first + steps):
@@ -178,13 +168,6 @@ def host_ema(snaps, decay, every=1, warmup=False, start=None, updates=0, first_s
     return e, updates
 
 
-def same_floats(got, want):
-    keys = [k for k, v in got.items() if v.is_floating_point()]
-    assert keys and set(keys) == {k for k, v in want.items() if v.is_floating_point()}
-    bad = [k for k in keys if not torch.equal(got[k], want[k])]
-    assert not bad, (len(bad), bad[:5])
-
-
 def test_trainer_equals_the_host_recurrence():
     r = run(5, ema_decay=0.9)
     tr = r["tr"]
@@ -209,15 +192,6 @@ def test_the_average_only_reads_the_model():
     assert on["losses"] == off["losses"] and on["metrics"] == off["metrics"]
     same_floats(on["snaps"][-1], off["snaps"][-1])
     assert all(torch.equal(a, b) for a, b in zip(on["m"], off["m"])) and all(torch.equal(a, b) for a, b in zip(on["v"], off["v"]))
-
-
-def recorded(**kw):
-    tr, head = make_trainer(launch="cmdlist", **kw)
-    for t in range(3):                                                    # eager, recording, replay
-        tr.train_step(*batch(MICRO, head, t))
-    torch.cuda.synchronize()
-    assert tr._cmds is not None and tr.launch == "cmdlist"
-    return tr, [(name, None if args is None else len(args)) for _, args, name in tr._cmds.cmds]
 
 
 def test_switched_off_it_issues_the_launches_of_a_trainer_without_the_argument():

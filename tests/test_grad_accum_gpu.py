@@ -10,18 +10,10 @@ from conftest import ROOT  # noqa: F401  (puts the repository root on sys.path)
 
 pytestmark = pytest.mark.gpu
 
-from cris.pytorch_amd import arch, hip, ops, synth  # noqa: E402
-from cris.pytorch_amd.engine import Comm  # noqa: E402
-from cris.pytorch_amd.trainer import NativeTrainer  # noqa: E402
+from cris.pytorch_amd import arch, hip, ops  # noqa: E402
+from trainer_cases import ADAM_TOL, MICRO, TwoEqualRanks, batch, make_trainer, relerr  # noqa: E402
 
 DEV = "cuda"
-ADAM_TOL = 1e-6          # relative L2 error of the existing Adam comparisons (tests/test_hip_ops.py test_adam_*, test_grad_clip_gpu.py)
-MICRO = 2                # samples per micro-batch
-
-
-def relerr(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return float((a - b).norm() / (b.norm() + 1e-30))
 
 
 # ---- the kernels ----------------------------------------------------------------------------------------------------
@@ -85,15 +77,6 @@ def test_step_advance_micro():
 
 
 # ---- the trainer ------------------------------------------------------------------------------------------------------
-def make_trainer(**kw):
-    clip, head = arch.specs_by_name("tiny")
-    return NativeTrainer(clip, head, arch.synthetic_state_dict(clip, head, 0), torch.device("cuda:0"), **kw), head
-
-
-def batch(n, head, t):
-    return [x.to("cuda:0") for x in synth.make_batch(n, 64, head.word_len, 0, t)]
-
-
 def run(steps, K=2, launch="eager", changes=None, **kw):
     """`steps` optimizer steps of K micro-batches of MICRO samples (K=None: a trainer built without the argument); changes:
     {step index: K set before that step}.  Per step: loss, metric, tracked norm, float64 norm of G / K; final parameters."""
@@ -248,30 +231,11 @@ def test_clipping_composes(k2):
     assert all(bool(torch.isfinite(p).all()) for p in c["params"].values())
 
 
-class TwoEqualRanksCounting(Comm):
-    """what a rank of a world of two sees when both ranks hold the same batch (test_grad_clip_gpu.py TwoEqualRanks), counting
-    the exchanges it is asked for"""
-    world = 2
-    supports_max_u8 = True
-
-    def __init__(self):
-        super().__init__()
-        self.calls = {"sum": 0, "max": 0}
-
-    def allreduce_async(self, t, op="sum"):
-        self.calls[op] += 1
-        if op == "sum":
-            t.mul_(2.0)
-
-    def wait_all(self):
-        pass
-
-
 def test_exchange_runs_once_per_optimizer_step(k2):
-    one = run(1, K=1, comm=TwoEqualRanksCounting())
+    one = run(1, K=1, comm=TwoEqualRanks())
     per_step = dict(one["tr"].comm.calls)
     assert per_step["sum"] == len(one["tr"].engine.stage_ranges) and per_step["max"] == 1
-    two = run(3, K=2, comm=TwoEqualRanksCounting())
+    two = run(3, K=2, comm=TwoEqualRanks())
     tr = two["tr"]
     assert tr.comm.world == 2 and tr.grad_exchange == "rccl"
     assert tr.comm.calls == {k: 3 * v for k, v in per_step.items()}, (tr.comm.calls, per_step)

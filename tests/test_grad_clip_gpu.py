@@ -10,22 +10,16 @@ from conftest import ROOT  # noqa: F401  (puts the repository root on sys.path)
 
 pytestmark = pytest.mark.gpu
 
-from cris.pytorch_amd import arch, hip, ops, synth  # noqa: E402
-from cris.pytorch_amd.engine import Comm  # noqa: E402
+from cris.pytorch_amd import arch, hip, ops  # noqa: E402
 from cris.pytorch_amd.trainer import NativeTrainer  # noqa: E402
+from trainer_cases import ADAM_TOL, TwoEqualRanks, batch, make_trainer, relerr  # noqa: E402
 
 DEV = "cuda"
-ADAM_TOL = 1e-6          # relative L2 error of the existing Adam comparisons (tests/test_hip_ops.py test_adam_*)
 
 
 def rnd(*shape, scale=1.0, seed=0):
     g = torch.Generator(device="cpu").manual_seed(seed + sum(shape))
     return torch.randn(*shape, generator=g) * scale
-
-
-def relerr(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return float((a - b).norm() / (b.norm() + 1e-30))
 
 
 def gemm_layout(g, Cpad, poison):
@@ -173,15 +167,12 @@ def test_clipped_update_equals_torch():
 def run_trainer(steps, launch="eager", changes=None, **kw):
     """`steps` train steps from the same state and batches; changes: {step index: max_norm set before that step}.
     Returns (trainer, losses, grad norms read from the trainer (or None), float64 norms of engine.G, parameters)."""
-    clip, head = arch.specs_by_name("tiny")
-    dev = torch.device("cuda:0")
-    tr = NativeTrainer(clip, head, arch.synthetic_state_dict(clip, head, 0), dev, launch=launch, **kw)
+    tr, head = make_trainer(launch=launch, **kw)
     losses, norms, norms64 = [], [], []
     for t in range(steps):
         if changes and t in changes:
             tr.set_max_norm(changes[t])
-        img, word, mask = synth.make_batch(2, 64, head.word_len, 0, t)
-        loss, _ = tr.train_step(img.to(dev), word.to(dev), mask.to(dev))
+        loss, _ = tr.train_step(*batch(2, head, t))
         losses.append(float(loss))
         if tr.max_norm > 0 or tr.track_grad_norm:
             norms.append(float(tr.grad_norm))
@@ -225,20 +216,6 @@ def test_trainer_clips_and_reports(unclipped):
     assert all(bool(torch.isfinite(p).all()) for p in params.values())
 
 
-class TwoEqualRanks(Comm):
-    """what a rank of a world of two sees when both ranks hold the same batch: the all-reduced (summed) gradient is twice its
-    own (exact in fp32), the MAX of the embedding-row marks is its own"""
-    world = 2
-    supports_max_u8 = True
-
-    def allreduce_async(self, t, op="sum"):
-        if op == "sum":
-            t.mul_(2.0)
-
-    def wait_all(self):
-        pass
-
-
 def test_norm_of_the_rank_averaged_gradient(unclipped):
     """the multi-rank placement: the norm is taken AFTER the gradient all-reduce and with the update's 1/world, so it is that
     of the averaged gradient.  Two ranks with equal batches average to the one-rank gradient (x 2, x 0.5: exact), so norms,
@@ -274,8 +251,8 @@ def test_arguments(unclipped):
         NativeTrainer(clip, head, arch.synthetic_state_dict(clip, head, 0), torch.device("cuda:0"), max_norm=-1)
     a, b = unclipped["max_norm"], 0.5 * unclipped["max_norm"]
     _, le, ne, _, pe = run_trainer(6, launch="eager", max_norm=a, changes={3: b})
-    clip_tr = NativeTrainer(clip, head, arch.synthetic_state_dict(clip, head, 0), torch.device("cuda:0"), launch="graph", max_norm=a)
-    dev, losses = torch.device("cuda:0"), []
+    clip_tr, _ = make_trainer(launch="graph", max_norm=a)
+    losses = []
     for t in range(6):
         if t == 3:
             assert clip_tr._graph is not None, clip_tr.graph_error
@@ -283,8 +260,7 @@ def test_arguments(unclipped):
                 clip_tr.set_max_norm(-2.0)
             clip_tr.set_max_norm(b)
             assert clip_tr._graph is None and clip_tr.max_norm == b      # dropped: the threshold is a launch argument
-        img, word, mask = synth.make_batch(2, 64, head.word_len, 0, t)
-        losses.append(float(clip_tr.train_step(img.to(dev), word.to(dev), mask.to(dev))[0]))
+        losses.append(float(clip_tr.train_step(*batch(2, head, t))[0]))
     torch.cuda.synchronize()
     assert clip_tr._graph is not None
     assert losses == le, (losses, le)

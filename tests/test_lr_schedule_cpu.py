@@ -12,10 +12,10 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "cris_hip.h")
 sys.path.insert(0, ROOT)
 
 from cris.pytorch_amd import hip, lr  # noqa: E402
+from header_decls import HEADER, ctype_of, prototypes  # noqa: E402
 
 NAME = "cris_adam_schedule_lrs"
 BASE = [1e-5, 1e-4]                 # two groups
@@ -27,20 +27,6 @@ def lib():
     import __graft_entry__ as g
     g.build()
     return hip.load()
-
-
-def ctype_of(decl):
-    """ctypes type of one C parameter declaration of the header"""
-    decl = decl.strip()
-    if "*" in decl:
-        return C.c_void_p
-    base = re.sub(r"\b(const|unsigned)\b", "", decl).split()[0]
-    return {"int": C.c_int, "long": C.c_long, "float": C.c_float, "int32_t": C.c_int, "uint32_t": C.c_uint}[base]
-
-
-def prototypes(src):
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return {m.group(2): (m.group(1), m.group(3)) for m in re.finditer(r"\b(int|long)\s+(cris_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src)}
 
 
 def test_signature_matches_the_prototype():

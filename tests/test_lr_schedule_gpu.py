@@ -12,11 +12,10 @@ from conftest import ROOT  # noqa: F401  (puts the repository root on sys.path)
 
 pytestmark = pytest.mark.gpu
 
-from cris.pytorch_amd import arch, hip, lr, synth  # noqa: E402
-from cris.pytorch_amd.trainer import NativeTrainer  # noqa: E402
+from cris.pytorch_amd import hip, lr  # noqa: E402
+from trainer_cases import MICRO, batch, make_trainer, recorded  # noqa: E402
 
 DEV = "cuda"
-MICRO = 2
 BASE = 1e-4
 # six distinct rows (backbone, rest), none of them the constructor's (BASE, BASE)
 T6 = np.array([[2e-5, 3e-4], [5e-5, 2.5e-4], [8e-5, 2e-4], [6e-5, 1.5e-4], [4e-5, 5e-5], [1e-5, 2e-5]], dtype=np.float32)
@@ -82,15 +81,6 @@ def test_kernel_copies_the_row_and_nothing_else(n_desc, n_groups):
 
 
 # ---- the trainer ------------------------------------------------------------------------------------------------------------
-def make_trainer(**kw):
-    clip, head = arch.specs_by_name("tiny")
-    return NativeTrainer(clip, head, arch.synthetic_state_dict(clip, head, 0), torch.device("cuda:0"), **kw), head
-
-
-def batch(n, head, t):
-    return [x.to("cuda:0") for x in synth.make_batch(n, 64, head.word_len, 0, t)]
-
-
 def rates(table, t):
     return tuple(float(x) for x in table[min(t, len(table) - 1)])
 
@@ -197,15 +187,6 @@ def test_replay_follows_the_table_from_device_state(launch):
     h = r["handles"]
     assert h[0] is None and h[1] is not None and all(x is h[1] for x in h[2:])
     assert (tr._graph if launch == "graph" else tr._cmds) is h[1]
-
-
-def recorded(**kw):
-    tr, head = make_trainer(launch="cmdlist", **kw)
-    for t in range(3):                                                    # eager, recording, replay
-        tr.train_step(*batch(MICRO, head, t))
-    torch.cuda.synchronize()
-    assert tr._cmds is not None and tr.launch == "cmdlist"
-    return tr, [(name, None if args is None else len(args)) for _, args, name in tr._cmds.cmds]
 
 
 def test_switched_off_it_issues_the_launches_of_a_trainer_without_the_argument():
