@@ -934,9 +934,18 @@ extern "C" int cris_train_metric(const float* logits, const float* target, int B
 
 struct adam_coef {
     float beta1, beta2, eps, wd, bc1, rsb2, gscale;
+    float keep;                                   // decoupled decay (cris_adamw_step): 1 - lr * wd of this tensor; else unused
 };
+// a product rounded on its own: HIP's __fmul_rn is a plain operator that hipcc still fuses into a following add or subtract
+__device__ __forceinline__ float adam_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 // torch.optim.Adam (non-amsgrad): step_size = lr / bias_correction1, denom = sqrt(v) / sqrt(bias_correction2) + eps
+// DW (cris_adamw_step, decoupled): p is first scaled by k.keep, rounded, and k.wd is 0 - AdamW's p *= 1 - lr * wd
+template <bool DW>
 __device__ __forceinline__ void adam_update(const adam_coef& k, float lr, float g, float& p, float& m, float& v) {
+    if (DW) p = adam_mul_rn(p, k.keep);
     g *= k.gscale;
     if (k.wd != 0.f) g += k.wd * p;
     m = k.beta1 * m + (1.f - k.beta1) * g;
@@ -947,7 +956,7 @@ __device__ __forceinline__ void adam_update(const adam_coef& k, float lr, float 
 // One tile of a GEMM weight: Adam on the fp32 master values AND the bf16 operand copies the next step's kernels read -
 // F [n][tap][Cpad] (forward) and D [c][taps-1-tap][Npad] (input gradient) - written from the freshly updated values through an
 // LDS tile, so the fp32 weights are not read a second time by a separate packing pass (1.8 GB / step at CRIS-R50).
-template <int PT>
+template <int PT, bool DW>
 __device__ __forceinline__ void adam_pack_tile(const cris_adam_desc& d, int lb, const adam_coef& k, bf16_t* tile) {
     constexpr int LROW = AP_LROW(PT);
     const int tiles_c = (d.cin + AP_T - 1) / AP_T;
@@ -966,7 +975,7 @@ __device__ __forceinline__ void adam_pack_tile(const cris_adam_desc& d, int lb, 
             const long pi = ((long)(n0 + n_l) * d.cin + c0) * PT + e;
             const long gi = d.taps > 0 ? ((long)(n0 + n_l) * PT + tap) * d.cpad + c0 + c_l : pi;
             float p = d.p[pi], m = d.m[pi], v = d.v[pi];
-            adam_update(k, d.lr, d.g[gi], p, m, v);
+            adam_update<DW>(k, d.lr, d.g[gi], p, m, v);
             d.p[pi] = p; d.m[pi] = m; d.v[pi] = v;
             tile[n_l * LROW + e] = f2bf(p);
         }
@@ -977,7 +986,7 @@ __device__ __forceinline__ void adam_pack_tile(const cris_adam_desc& d, int lb, 
             if (n_l >= rows) continue;
             const long pi = (long)(c0 + c_l) * d.N + n0 + n_l;
             float p = d.p[pi], m = d.m[pi], v = d.v[pi];
-            adam_update(k, d.lr, d.g[pi], p, m, v);
+            adam_update<DW>(k, d.lr, d.g[pi], p, m, v);
             d.p[pi] = p; d.m[pi] = m; d.v[pi] = v;
             tile[n_l * LROW + c_l * PT] = f2bf(p);
         }
@@ -1002,10 +1011,13 @@ __device__ __forceinline__ void adam_pack_tile(const cris_adam_desc& d, int lb, 
     }
 }
 
-template <int PT>
+// MODE 0: one weight decay `wd` for the whole table, coupled (cris_adam_step[_amp]).  MODE 1 / 2 (cris_adamw_step): the decay of
+// descriptor i is decay_of[i] (`wd` is ignored), coupled (1) or decoupled (2).
+template <int PT, int MODE>
 __global__ __launch_bounds__(256) void adam_kernel(const cris_adam_desc* __restrict__ tab, int n_desc, float beta1, float beta2, float eps,
                                                    float wd, float bc1, float bc2, float gscale, const int* __restrict__ step_dev,
-                                                   const float* __restrict__ loss_scale_dev, const float* __restrict__ skip_dev) {
+                                                   const float* __restrict__ loss_scale_dev, const float* __restrict__ skip_dev,
+                                                   const float* __restrict__ decay_of) {
     extern __shared__ __attribute__((aligned(16))) unsigned char adam_smem[];
     // torch.amp.GradScaler semantics on the device (cris_adam_step_amp): the whole update is skipped when the scaler found a
     // non-finite gradient, and the gradients still carry the loss scale - no host synchronisation, no separate unscale pass
@@ -1029,10 +1041,12 @@ __global__ __launch_bounds__(256) void adam_kernel(const cris_adam_desc* __restr
         if (tab[mid].block_start <= bid) lo = mid; else hi = mid - 1;
     }
     const cris_adam_desc d = tab[lo];
+    if (MODE != 0) wd = decay_of[lo];     // block-uniform: every block of a tensor sees its tensor's decay
     adam_coef k;
-    k.beta1 = beta1; k.beta2 = beta2; k.eps = eps; k.wd = wd; k.bc1 = bc1; k.rsb2 = rsqrtf(bc2); k.gscale = gscale;
+    k.beta1 = beta1; k.beta2 = beta2; k.eps = eps; k.wd = MODE == 2 ? 0.f : wd; k.bc1 = bc1; k.rsb2 = rsqrtf(bc2); k.gscale = gscale;
+    k.keep = MODE == 2 ? (float)(1.0 - (double)d.lr * (double)wd) : 1.f;       // d.lr: this step's rate (cris_adam_schedule_lrs)
     if (d.dstF || d.dstD) {               // block-uniform
-        adam_pack_tile<PT>(d, bid - d.block_start, k, reinterpret_cast<bf16_t*>(adam_smem));
+        adam_pack_tile<PT, MODE == 2>(d, bid - d.block_start, k, reinterpret_cast<bf16_t*>(adam_smem));
         return;
     }
     const long base = (long)(bid - d.block_start) * ADAM_ELEMS;
@@ -1050,7 +1064,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const cris_adam_desc* __restr
             gi = (n * d.taps + tap) * d.cpad + c;
         }
         float p = d.p[i], m = d.m[i], v = d.v[i];
-        adam_update(k, d.lr, d.g[gi], p, m, v);
+        adam_update<MODE == 2>(k, d.lr, d.g[gi], p, m, v);
         d.p[i] = p; d.m[i] = m; d.v[i] = v;
     }
 }
@@ -1092,23 +1106,50 @@ extern "C" int cris_unpack_grads(const cris_adam_desc* dev_table, int n_desc, in
     CRIS_LAUNCH_CHECK();
     return 0;
 }
+// the one launch behind cris_adam_step[_amp] (MODE 0) and cris_adamw_step (MODE 1 / 2); `fn`: the caller, for cris_last_error()
+template <int MODE>
+static int adam_launch(const char* fn, const cris_adam_desc* dev_table, int n_desc, int total_blocks, float beta1, float beta2, float eps,
+                       float weight_decay, const float* decay_of, float bias_corr1, float bias_corr2, float grad_scale,
+                       const int32_t* step_dev, const float* loss_scale_dev, const float* skip_dev, int pack_taps, void* stream) {
+    typedef void (*adam_fn)(const cris_adam_desc*, int, float, float, float, float, float, float, float, const int*, const float*, const float*,
+                            const float*);
+    const adam_fn k9 = adam_kernel<9, MODE>, k1 = adam_kernel<1, MODE>;
+    constexpr int LDS9 = AP_TN(9) * AP_LROW(9) * 2, LDS1 = AP_TN(1) * AP_LROW(1) * 2;
+    static const int ready = (int)hipFuncSetAttribute((const void*)k9, hipFuncAttributeMaxDynamicSharedMemorySize, LDS9);
+    if (ready != 0) {
+        cris_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (%d)", fn, ready);
+        return ready;
+    }
+    hipLaunchKernelGGL(pack_taps == 9 ? k9 : k1, dim3(total_blocks), dim3(256), pack_taps == 9 ? LDS9 : LDS1, (hipStream_t)stream, dev_table,
+                       n_desc, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale, step_dev, loss_scale_dev, skip_dev,
+                       decay_of);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        cris_set_error("%s: launch failed: %s", fn, hipGetErrorString(e));
+        return (int)e;
+    }
+    return 0;
+}
 extern "C" int cris_adam_step_amp(const cris_adam_desc* dev_table, int n_desc, int total_blocks, float beta1, float beta2, float eps,
                                   float weight_decay, float bias_corr1, float bias_corr2, float grad_scale, const int32_t* step_dev,
                                   const float* loss_scale_dev, const float* skip_dev, int pack_taps, void* stream) {
     CRIS_CHECK_ARG(dev_table && n_desc > 0 && total_blocks > 0, "empty table");
     CRIS_CHECK_ARG(pack_taps == 1 || pack_taps == 9, "a table holds tensors packed with 1 tap (and unpacked ones) or with 9 taps");
-    typedef void (*adam_fn)(const cris_adam_desc*, int, float, float, float, float, float, float, float, const int*, const float*, const float*);
-    const adam_fn k9 = adam_kernel<9>, k1 = adam_kernel<1>;
-    constexpr int LDS9 = AP_TN(9) * AP_LROW(9) * 2, LDS1 = AP_TN(1) * AP_LROW(1) * 2;
-    static const int ready = (int)hipFuncSetAttribute((const void*)k9, hipFuncAttributeMaxDynamicSharedMemorySize, LDS9);
-    if (ready != 0) {
-        cris_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (%d)", __func__, ready);
-        return ready;
-    }
-    hipLaunchKernelGGL(pack_taps == 9 ? k9 : k1, dim3(total_blocks), dim3(256), pack_taps == 9 ? LDS9 : LDS1, (hipStream_t)stream, dev_table,
-                       n_desc, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale, step_dev, loss_scale_dev, skip_dev);
-    CRIS_LAUNCH_CHECK();
-    return 0;
+    return adam_launch<0>(__func__, dev_table, n_desc, total_blocks, beta1, beta2, eps, weight_decay, nullptr, bias_corr1, bias_corr2,
+                          grad_scale, step_dev, loss_scale_dev, skip_dev, pack_taps, stream);
+}
+// cris_adam_step_amp with one decay per descriptor, coupled or decoupled (AdamW): include/cris_hip.h
+extern "C" int cris_adamw_step(const cris_adam_desc* dev_table, int n_desc, int total_blocks, float beta1, float beta2, float eps,
+                               const float* decay_of, int decoupled, float bias_corr1, float bias_corr2, float grad_scale,
+                               const int32_t* step_dev, const float* loss_scale_dev, const float* skip_dev, int pack_taps, void* stream) {
+    CRIS_CHECK_ARG(dev_table, "null dev_table");
+    CRIS_CHECK_ARG(decay_of, "null decay_of");
+    CRIS_CHECK_ARG(n_desc >= 1, "n_desc must be >= 1");
+    CRIS_CHECK_ARG(total_blocks >= 1, "total_blocks must be >= 1");
+    CRIS_CHECK_ARG(pack_taps == 1 || pack_taps == 9, "pack_taps must be 1 or 9");
+    CRIS_CHECK_ARG(decoupled == 0 || decoupled == 1, "decoupled must be 0 or 1");
+    return (decoupled ? adam_launch<2> : adam_launch<1>)(__func__, dev_table, n_desc, total_blocks, beta1, beta2, eps, 0.f, decay_of, bias_corr1,
+                                                         bias_corr2, grad_scale, step_dev, loss_scale_dev, skip_dev, pack_taps, stream);
 }
 
 extern "C" int cris_adam_step(const cris_adam_desc* dev_table, int n_desc, int total_blocks, float beta1, float beta2, float eps,

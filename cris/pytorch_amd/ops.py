@@ -975,7 +975,7 @@ class AdamTable:
         packs[i]: None or (dstF, dstD, N, Cin, taps, Cpad, Npad, transposed) - the bf16 GEMM-operand copies of tensor i
         (PackTable layouts) that the update rewrites from the new values.
         row_live: {i: uint8 tensor [rows of tensor i]} - rows whose byte is 0 have never had a gradient and are skipped
-        (bit-identical to the dense update while weight_decay == 0; cris_adam_desc.row_live)."""
+        (bit-identical to the dense update while the tensor's weight decay is 0, and only then; cris_adam_desc.row_live)."""
         lib = hip.load()
         self.m = [torch.zeros_like(p) for p in params]
         self.v = [torch.zeros_like(p) for p in params]
@@ -1016,6 +1016,7 @@ class AdamTable:
         self.row_live = dict(row_live) if row_live else {}
         self.keep = [pk[:2] for pk in self.packs if pk is not None]
         self.step_count = 0
+        self.decays, self.decoupled, self._decay_dev = None, False, None      # set_decay
         # grad_norm(): one partial sum of squares per block of either table, and [norm, divisor] - allocated once (stable
         # addresses for graph replay)
         self._partials = torch.empty(max(sum(t.total_blocks for t in self.tables.values()), 1), dtype=torch.float32, device=self.device)
@@ -1028,6 +1029,45 @@ class AdamTable:
             for j, i in enumerate(idx):
                 t.arr[j].lr = self.lrs[i]
             t.upload(self.device)
+
+    @staticmethod
+    def checked_decay(what, value):
+        """`value` as a float, or ValueError: a finite number >= 0 (not a bool)"""
+        import math
+        import numbers
+        if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value) or value < 0:
+            raise ValueError("%s must be a finite number >= 0, got %r" % (what, value))
+        return float(value)
+
+    @staticmethod
+    def checked_decays(decays, n=None):
+        """`decays` as a list of floats (n of them when n is given), or ValueError"""
+        try:
+            decays = list(decays)
+        except TypeError:
+            raise ValueError("decays must be a sequence of numbers, one per tensor, got %r" % (decays,))
+        decays = [AdamTable.checked_decay("decays[%d]" % i, w) for i, w in enumerate(decays)]
+        if n is not None and len(decays) != n:
+            raise ValueError("%d decays for %d tensors" % (len(decays), n))
+        return decays
+
+    def set_decay(self, decays, decoupled=False):
+        """decays: one weight decay per tensor, in the order of `params` (finite, >= 0), applied coupled (g += wd * p, the rule of
+        step(weight_decay=...)) or decoupled (AdamW: p *= 1 - lr * wd with the rate the table holds at that step); step() then
+        calls cris_adamw_step.  None: back to the one scalar of step().  Everything is validated before a device is touched.  The
+        values live in one device float array per non-empty table, ordered like index[taps], allocated once and rewritten in
+        place afterwards (a captured graph keeps valid addresses)."""
+        if decays is None:
+            self.decays, self.decoupled = None, False
+            return
+        if not isinstance(decoupled, bool):
+            raise ValueError("decoupled must be a bool, got %r" % (decoupled,))
+        decays = self.checked_decays(decays, len(self.params))
+        self.decays, self.decoupled = decays, decoupled
+        if self._decay_dev is None:
+            self._decay_dev = {taps: torch.zeros(len(idx), dtype=torch.float32, device=self.device) for taps, idx in self.index.items() if idx}
+        for taps, dev in self._decay_dev.items():
+            dev.copy_(torch.tensor([decays[i] for i in self.index[taps]], dtype=torch.float32))
 
     @property
     def refreshes_packs(self):
@@ -1054,13 +1094,21 @@ class AdamTable:
     def step(self, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0, step_dev=None, loss_scale_dev=None, skip_dev=None):
         """step_dev: optional int32 device tensor holding the 1-based step count (graph replay); else a host counter.
         loss_scale_dev / skip_dev: GradScaler's scale and found_inf (device fp32 scalars): gradients are divided by the scale
-        inside the update, a non-zero found_inf skips it (cris_adam_step_amp)"""
+        inside the update, a non-zero found_inf skips it (cris_adam_step_amp).  While set_decay holds a list the decays are
+        that list's (cris_adamw_step) and `weight_decay` must stay 0."""
+        if self.decays is not None and weight_decay != 0.0:
+            raise ValueError("weight_decay = %r next to per-tensor decays (set_decay): pass one or the other" % (weight_decay,))
         self.step_count += 1
         bc1 = 1.0 - beta1 ** self.step_count
         bc2 = 1.0 - beta2 ** self.step_count
         for taps in (9, 1):
             t = self.tables[taps]
-            if t.n:
+            if not t.n:
+                continue
+            if self.decays is not None:
+                hip.call("cris_adamw_step", ptr(t.dev), t.n, t.total_blocks, beta1, beta2, eps, ptr(self._decay_dev[taps]),
+                         1 if self.decoupled else 0, bc1, bc2, grad_scale, ptr(step_dev), ptr(loss_scale_dev), ptr(skip_dev), taps, _stream())
+            else:
                 hip.call("cris_adam_step_amp", ptr(t.dev), t.n, t.total_blocks, beta1, beta2, eps, weight_decay, bc1, bc2,
                          grad_scale, ptr(step_dev), ptr(loss_scale_dev), ptr(skip_dev), taps, _stream())
 

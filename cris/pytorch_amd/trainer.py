@@ -39,6 +39,16 @@ optimizer step t, steps past the end use the last row - lives on the device (ops
 the `lr` fields of the Adam descriptors, where the Adam kernels read it: warm-up, cosine, one-cycle or any other per-iteration
 schedule (cris.pytorch_amd.lr builds the tables) without host work and without a new capture.  Once per optimizer step, no
 communication (every rank passes the same table).  With lr_schedule=None (the default) the step issues the launches it always did.
+
+Weight decay (`weight_decay=w`, `decoupled_weight_decay`, `no_decay`): by default w is one scalar, applied as coupled L2 (g += w * p
+before the moments) to every tensor, the reference's torch.optim.Adam.  `decoupled_weight_decay=True` makes it AdamW's
+p *= 1 - lr * w on the weight itself, gradient and moments untouched, with the rate of the running step (the schedule's row when
+there is one).  `no_decay` is a rule (name, tensor) -> bool that exempts tensors: no_decay_1d (biases, BatchNorm / LayerNorm scales
+- what the reference's utils/misc.py:168-189 group_weight exempts) and no_decay_1d_and_positional (the positional embeddings too -
+the `backbone_no_decay` group model/__init__.py:4-29 keeps commented out) are ready-made.  Either makes the Adam launches
+`cris_adamw_step`, which reads one decay per tensor from a small device array: the same two launches, once per optimizer step,
+independent of clipping (the norm is the raw gradient's), no communication.  With the defaults the step issues the launches it
+always did - `cris_adam_step_amp` with the scalar - and nothing is allocated.
 """
 import contextlib
 import os
@@ -80,9 +90,24 @@ def epoch_group_lrs(epoch, base_lr, lr_multi, milestones, gamma):
     return lr_multi * base_lr * f, base_lr * f
 
 
+EMBEDDING = "backbone.token_embedding.weight"          # the tensor whose rows the update may skip (NativeTrainer.__init__)
+
+
 def in_backbone_group(name):
     """`build_segmenter`'s name rule (model/__init__.py:36-48): group 0 = backbone without the positional embeddings, group 1 = the rest"""
     return name.startswith("backbone") and "positional_embedding" not in name
+
+
+def no_decay_1d(name, tensor):
+    """no_decay rule: every parameter with at most one dimension - biases and BatchNorm / LayerNorm scales, the `weight_decay=0`
+    group of the reference's group_weight (utils/misc.py:168-189)"""
+    return tensor.dim() <= 1
+
+
+def no_decay_1d_and_positional(name, tensor):
+    """no_decay rule: no_decay_1d plus the positional embeddings, the reference's commented-out `backbone_no_decay` group
+    (model/__init__.py:4-29)"""
+    return tensor.dim() <= 1 or "positional_embedding" in name
 
 
 def checked_int(what, value, lowest):
@@ -95,8 +120,11 @@ class NativeTrainer:
     def __init__(self, clip: ClipSpec, head: HeadSpec, state_dict, device, base_lr=1e-4, lr_multi=0.1, weight_decay=0.0,
                  comm=None, sync_bn=False, use_graph: Optional[bool] = None, launch: Optional[str] = None, max_norm: float = 0.0,
                  track_grad_norm: bool = False, accum_steps: int = 1, ema_decay: Optional[float] = None, ema_every: int = 1,
-                 ema_warmup: bool = False, lr_schedule=None):
-        """lr_schedule = array-like [n_steps, 2]: the (backbone, rest) learning rates of every optimizer step, followed on the device
+                 ema_warmup: bool = False, lr_schedule=None, decoupled_weight_decay: bool = False, no_decay=None):
+        """weight_decay = w >= 0: coupled L2 on every tensor (the reference's Adam); decoupled_weight_decay: AdamW's p *= 1 - lr * w
+        instead; no_decay: None or a rule (name, tensor) -> bool, True = this tensor's decay is 0 (no_decay_1d,
+        no_decay_1d_and_positional) - the module docstring; set_weight_decay; weight_decays.
+        lr_schedule = array-like [n_steps, 2]: the (backbone, rest) learning rates of every optimizer step, followed on the device
         inside the captured step (the module docstring; set_lr_schedule; cris.pytorch_amd.lr builds such tables).
         ema_decay = d in (0, 1): keep an exponential moving average of parameters and BatchNorm statistics, updated every
         `ema_every`-th optimizer step with weight 1 - d (ema_warmup: 1 - min(d, (1 + t) / (10 + t)) for update t); set_ema.
@@ -108,6 +136,10 @@ class NativeTrainer:
         self.accum_steps = checked_int("accum_steps", accum_steps, 1)
         ema_cfg = self._checked_ema(ema_decay, ema_every, ema_warmup)
         lr_schedule = self._checked_schedule(lr_schedule)
+        decay_cfg = self._checked_weight_decay(weight_decay, decoupled_weight_decay, no_decay)
+        if no_decay is not None:                 # (the rule's answers are checked on the tensors as given, before a device is touched)
+            self._exempt(no_decay, [(k, v) for k, v in strip_ddp_prefix(state_dict).items()
+                                    if v.is_floating_point() and not k.endswith(("running_mean", "running_var"))])
         self.device = device
         params, buffers = split_state_dict(state_dict, device)
         self.engine = Engine(clip, head, params, buffers, device, comm=comm, sync_bn=sync_bn)
@@ -124,18 +156,22 @@ class NativeTrainer:
         names = [n for n in e.grad_order if n != "backbone.logit_scale"]          # never receives a gradient (unused)
         self.names = names
         self.group = {n: (0 if in_backbone_group(n) else 1) for n in names}
-        self.base_lr, self.lr_multi, self.weight_decay = base_lr, lr_multi, weight_decay
+        self.base_lr, self.lr_multi = base_lr, lr_multi
+        self.weight_decay, self.decoupled_weight_decay, self.no_decay = decay_cfg
+        self._no_decay_names = self._exempt(no_decay, [(n, e.P[n]) for n in names])
         # Rows of the token embedding (49408 x 512: 17% of the parameters) that have never received a gradient keep g = m = v = 0
         # and Adam leaves them exactly as they are (while weight_decay == 0): the embedding backward marks the rows of each
-        # batch's tokens and the update skips the rest - bit-identical to the dense update.  With more ranks the all-reduced
+        # batch's tokens and the update skips the rest - bit-identical to the dense update while the embedding's own decay is 0
+        # (no weight decay at all, or the embedding exempt through `no_decay`).  With more ranks the all-reduced
         # gradient has the other ranks' rows too: the marks (sticky bytes) are then all-reduced with MAX next to the text
         # encoder's gradient stage (round 6; 49 KB per step on the gradient communicator), so every rank skips exactly the rows
         # no rank ever touched - communicators without a byte-wise MAX (dist.RcclComm) keep the dense update.
         # CRIS_ADAM_ROW_SKIP=0 switches it off.
-        if ((self.comm.world == 1 or getattr(self.comm, "supports_max_u8", False)) and weight_decay == 0.0
+        if ((self.comm.world == 1 or getattr(self.comm, "supports_max_u8", False)) and self.weight_decays[EMBEDDING] == 0.0
                 and os.environ.get("CRIS_ADAM_ROW_SKIP", "1") == "1" and torch.device(device).type == "cuda"):
             e.embed_live = torch.zeros(e.P["backbone.token_embedding.weight"].shape[0], dtype=torch.uint8, device=device)
         self._build_adam([base_lr] * len(names))
+        self._apply_weight_decay()
         self.metric = torch.zeros(2, device=device)
         # per-step device state: steps done (int32) and the dropout seed of the running step
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=device)
@@ -196,7 +232,7 @@ class NativeTrainer:
     def _build_adam(self, lrs):
         e, names = self.engine, self.names
         lr_of = dict(zip(names, lrs))
-        live = {names.index("backbone.token_embedding.weight"): e.embed_live} if e.embed_live is not None else None
+        live = {names.index(EMBEDDING): e.embed_live} if e.embed_live is not None else None
         self.adam = ops.AdamTable([e.P[n] for n in names], [e.G[n] for n in names], [lr_of[n] for n in names],
                                   layouts=[e.gemm_layout(n) for n in names], packs=[e.pack_info.get(n) for n in names], row_live=live)
 
@@ -265,10 +301,55 @@ class NativeTrainer:
             self._ema = None
         elif self._ema is None:
             e = self.engine
-            name = "backbone.token_embedding.weight"
-            self._ema = ops.EmaTable(list(e.P.items()) + list(e.Bf.items()),
-                                     row_live={name: e.embed_live} if e.embed_live is not None else None)
+            skip = e.embed_live is not None and self.weight_decays[EMBEDDING] == 0.0      # (a decayed row moves without a gradient)
+            self._ema = ops.EmaTable(list(e.P.items()) + list(e.Bf.items()), row_live={EMBEDDING: e.embed_live} if skip else None)
             self._ema.reset()
+        self._invalidate()
+
+    @staticmethod
+    def _checked_weight_decay(weight_decay, decoupled, no_decay):
+        """(weight_decay as a float, decoupled as a bool, no_decay), or ValueError"""
+        if no_decay is not None and not callable(no_decay):
+            raise ValueError("no_decay must be None or a callable (name, tensor) -> bool, got %r" % (no_decay,))
+        return ops.AdamTable.checked_decay("weight_decay", weight_decay), bool(decoupled), no_decay
+
+    @staticmethod
+    def _exempt(no_decay, named):
+        """names of the (name, tensor) pairs the rule exempts from weight decay; ValueError for an answer that is not a bool"""
+        out = set()
+        if no_decay is None:
+            return out
+        for n, t in named:
+            r = no_decay(n, t)
+            if not isinstance(r, bool):
+                raise ValueError("no_decay(%r, tensor) must return a bool, got %r" % (n, r))
+            if r:
+                out.add(n)
+        return out
+
+    @property
+    def weight_decays(self):
+        """{name: the weight decay tensor `name` is updated with}: weight_decay, or 0 where `no_decay` exempts it"""
+        return {n: (0.0 if n in self._no_decay_names else self.weight_decay) for n in self.names}
+
+    def _apply_weight_decay(self):
+        """one decay per tensor in the Adam tables (cris_adamw_step) when the decay is decoupled or some tensor is exempt; else the
+        scalar of cris_adam_step_amp, as always"""
+        per_tensor = self.decoupled_weight_decay or bool(self._no_decay_names)
+        wd = self.weight_decays
+        self.adam.set_decay([wd[n] for n in self.names] if per_tensor else None, self.decoupled_weight_decay)
+
+    def set_weight_decay(self, weight_decay, decoupled=False, no_decay=None):
+        """change the weight decay, whether it is decoupled and which tensors are exempt (all three: the constructor's arguments);
+        the step is captured / recorded again.  The marks of the token-embedding row skip are allocated by the constructor only
+        (when the embedding's own decay is 0 there); when the embedding becomes decayed the update ignores them (its rows move
+        without a gradient), and a running weight average stops skipping rows for good."""
+        cfg = self._checked_weight_decay(weight_decay, decoupled, no_decay)
+        exempt = self._exempt(no_decay, [(n, self.engine.P[n]) for n in self.names])
+        (self.weight_decay, self.decoupled_weight_decay, self.no_decay), self._no_decay_names = cfg, exempt
+        self._apply_weight_decay()
+        if self._ema is not None and self.weight_decays[EMBEDDING] != 0.0:
+            self._ema.drop_row_live()
         self._invalidate()
 
     @staticmethod
@@ -417,7 +498,8 @@ class NativeTrainer:
                 divisor = gn[1:2]
         if self._lr is not None:                 # the row of step_dev, which micro-batch 0 advanced
             self._lr.apply(self.step_dev)
-        self.adam.step(weight_decay=self.weight_decay, grad_scale=grad_scale, step_dev=self.step_dev, loss_scale_dev=divisor)
+        self.adam.step(weight_decay=0.0 if self.adam.decays is not None else self.weight_decay, grad_scale=grad_scale,
+                       step_dev=self.step_dev, loss_scale_dev=divisor)
         self.engine.packs_current = self.adam.refreshes_packs
         if self._ema is not None:
             self._ema.update(self.step_dev, self.ema_every, self.ema_decay, self.ema_warmup)
@@ -557,7 +639,9 @@ class NativeTrainer:
     def optimizer_state_dict(self):
         """Adam state in torch.optim.Adam.state_dict() form, loadable by the optimizer `train.py:105-107` builds from
         `build_segmenter`'s param_list (and by load_optimizer_state_dict).  With a per-step schedule the groups' `lr` is the row
-        the NEXT step will use (as torch reports it after scheduler.step()); the table itself is not saved."""
+        the NEXT step will use (as torch reports it after scheduler.step()); the table itself is not saved.  With decoupled decay
+        both groups carry `decoupled_weight_decay: True` (torch.optim.Adam's own key), with exempt tensors each group carries
+        `no_decay_params`, the indices of its exempt parameters; with the defaults neither key exists."""
         g0, g1 = self._param_order()
         idx = {n: i for i, n in enumerate(self.names)}
         lr_of = dict(zip(self.names, self.adam.lrs))
@@ -572,14 +656,21 @@ class NativeTrainer:
                             "exp_avg_sq": self.adam.v[j].detach().cpu().clone()}
         def group(names, initial_lr, first):
             lr = next((lr_of[n] for n in names if n in lr_of), self.base_lr)
-            return {"lr": lr, "initial_lr": initial_lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": self.weight_decay,
-                    "amsgrad": False, "params": list(range(first, first + len(names)))}
+            g = {"lr": lr, "initial_lr": initial_lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": self.weight_decay,
+                 "amsgrad": False, "params": list(range(first, first + len(names)))}
+            if self.decoupled_weight_decay:
+                g["decoupled_weight_decay"] = True
+            if self._no_decay_names:
+                g["no_decay_params"] = [first + i for i, n in enumerate(names) if n in self._no_decay_names]
+            return g
         return {"state": state, "param_groups": [group(g0, self.lr_multi * self.base_lr, 0), group(g1, self.base_lr, len(g0))]}
 
     def load_optimizer_state_dict(self, sd):
         """restore m / v / step count (and the group learning rates) from optimizer_state_dict() or from the state_dict of a
         torch.optim.Adam over the same param_list.  The groups' `lr` become the host's rates through set_group_lrs; a state saved
-        under a per-step schedule holds a row of its table there (set_lr_schedule)."""
+        under a per-step schedule holds a row of its table there (set_lr_schedule).  The weight-decay settings (`weight_decay`,
+        `decoupled_weight_decay`, `no_decay_params`) are configuration like the schedule table and are NOT restored: they stay
+        what the constructor or set_weight_decay made them."""
         g0, g1 = self._param_order()
         idx = {n: i for i, n in enumerate(self.names)}
         step = 0

@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -572,6 +572,23 @@ int cris_adam_step(const cris_adam_desc* dev_table, int n_desc, int total_blocks
 int cris_adam_step_amp(const cris_adam_desc* dev_table, int n_desc, int total_blocks, float beta1, float beta2, float eps,
                        float weight_decay, float bias_corr1, float bias_corr2, float grad_scale, const int32_t* step_dev,
                        const float* loss_scale_dev, const float* skip_dev, int pack_taps, void* stream);
+/* cris_adam_step_amp with one weight decay per tensor instead of one for the table: decay_of[i] (device, fp32, finite, >= 0) belongs
+ * to dev_table[i], and every block of a tensor reads its tensor's value.
+ *   decoupled == 0: the coupled rule of cris_adam_step, g += decay_of[i] * p before the moments.  With every entry equal to w the
+ *     result is, bit for bit, that of cris_adam_step_amp(weight_decay = w), w = 0 included.
+ *   decoupled == 1 (AdamW, torch.optim.AdamW): keep = (float)(1.0 - (double)lr * (double)decay_of[i]) once per block, lr read from
+ *     the descriptor (so after cris_adam_schedule_lrs on the same stream the decay follows the scheduled rate of this step); per
+ *     element p = p * keep, rounded on its own (never fused into the subtraction that follows), then the update of
+ *     cris_adam_step_amp with weight_decay = 0: gradient and moments do not see the decay.  "Scale the parameters by keep, then
+ *     cris_adam_step_amp(weight_decay = 0)" gives the same bits.
+ * Plain tensors, GEMM-layout gradients and the 1- and 9-tap packed tiles alike; the bf16 operand copies are written from the decayed
+ * and updated values.  row_live of descriptor i is honoured exactly when decay_of[i] == 0 (a decayed row moves without a gradient).
+ * loss_scale_dev, skip_dev, step_dev and pack_taps as for cris_adam_step_amp.  Non-zero with cris_last_error() before anything is
+ * launched: a null dev_table or decay_of; n_desc < 1; total_blocks < 1; pack_taps not 1 or 9; decoupled not 0 or 1. */
+int cris_adamw_step(const cris_adam_desc* dev_table, int n_desc, int total_blocks, float beta1, float beta2, float eps,
+                    const float* decay_of /*[n_desc], device*/, int decoupled, float bias_corr1, float bias_corr2,
+                    float grad_scale, const int32_t* step_dev, const float* loss_scale_dev, const float* skip_dev,
+                    int pack_taps, void* stream);
 int cris_counter_advance_unless(int32_t* counter, const float* skip, void* stream);
 int cris_adam_blocks(const cris_adam_desc* d);       /* blocks one descriptor occupies (host: block_start prefix sums) */
 int cris_adam_block_elems(void);

@@ -1,12 +1,13 @@
 """What the options of NativeTrainer cost per train step, and the proof that a change of the trainer changed nothing.
 
-Timing (profiles/grad_clip.md, grad_accum.md, ema.md, lr_schedule.md, trainer_refactor.md): the trainer at BASELINE.json configs[1]
+Timing (profiles/grad_clip.md, grad_accum.md, ema.md, lr_schedule.md, trainer_refactor.md, adamw.md): the trainer at BASELINE.json configs[1]
 (R50, 416 x 416, micro-batch 8, one GPU, the whole optimizer step as one captured graph), one ARM per row of the table below, each
 timed in fresh processes that alternate between the arms - and, with --parent DIR, the same arms run from a built checkout of the
 commit to compare against - so that drift of the machine lands on all of them alike.  Each process warms up, then times `--windows`
 windows of `--steps` micro-batches with a host clock around a device synchronise and reports the median window and the peak device
 memory of the torch allocator.  An arm of this tree is judged against the parent's arm of the same name: its median has to lie
-within the parent processes' own spread (max - min) of the parent's median.
+within the parent processes' own spread (max - min) of the parent's median.  An arm whose constructor arguments the parent's
+trainer does not know (adamw, adamw_schedule against a commit before them) runs from this tree only.
     python tools/trainer_bench.py [--arms plain,schedule,all] [--parent ../parent-checkout] --rounds 4 [--out result.json] [--md table.md]
 
 --check: every arm in each of the launch modes eager / graph / cmdlist, and `plain` and `all` once more with CRIS_FORCE_DIST=1 (the
@@ -31,6 +32,7 @@ import time
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCHEDULE = "warm-up + cosine, one row per step"          # (the table needs the number of steps: the worker builds it)
+NO_DECAY = "no_decay_1d_and_positional"                   # (a rule of the package under --root: the worker looks it up)
 ARMS = {                                                  # name -> constructor arguments
     "plain": {},
     "clip": {"max_norm": 1.0},                            # three more launches: two cris_grad_sumsq, one cris_grad_clip_finalize
@@ -40,6 +42,10 @@ ARMS = {                                                  # name -> constructor 
     "ema_every4": {"ema_decay": 0.999, "ema_every": 4},   # the same two; three steps in four the update returns at once
     "schedule": {"lr_schedule": SCHEDULE},                # one more launch per Adam table: cris_adam_schedule_lrs
     "all": {"max_norm": 1.0, "accum_steps": 2, "ema_decay": 0.999, "ema_every": 1, "lr_schedule": SCHEDULE},
+    # decoupled decay with the usual exemptions: the Adam launches become cris_adamw_step (not part of `all`, whose recorded list
+    # is compared with parents that do not have them)
+    "adamw": {"weight_decay": 0.01, "decoupled_weight_decay": True, "no_decay": NO_DECAY},
+    "adamw_schedule": {"weight_decay": 0.01, "decoupled_weight_decay": True, "no_decay": NO_DECAY, "lr_schedule": SCHEDULE},
 }
 CHECK_MAX_NORM = 1e-3                                     # --check: far below the tiny spec's gradient norm, so that it does clip
 CHECK_STEPS = 4                                           # eager, capture / recording, two replays
@@ -72,8 +78,11 @@ def make_trainer(args, spec, n_steps):
     import torch
     from cris.pytorch_amd import arch, debug, lr
     from cris.pytorch_amd.engine import Comm
+    from cris.pytorch_amd import trainer
     from cris.pytorch_amd.trainer import NativeTrainer
     kw, table = dict(ARMS[args.arm]), None
+    if "no_decay" in kw:
+        kw["no_decay"] = getattr(trainer, kw["no_decay"])
     if "lr_schedule" in kw:
         kw["lr_schedule"] = table = lr.with_warmup(lr.cosine([1e-5, 1e-4], n_steps), max(n_steps // 10, 1), 0.01)
     if args.check and "max_norm" in kw:
@@ -169,6 +178,13 @@ def check_worker(args):
     print("RESULT " + json.dumps(res), flush=True)
 
 
+def knows(root, arm):
+    """does the trainer of the tree at `root` take every constructor argument of `arm`?  (read from its source: no import)"""
+    with open(os.path.join(root, "cris", "pytorch_amd", "trainer.py")) as f:
+        src = f.read()
+    return all(k in src for k in ARMS[arm])
+
+
 def run_worker(label, root, arm, extra=(), env=None):
     """one fresh process, under its own time limit; the driver ends at the first that fails and starts nothing after it.  The
     worker is THIS file for every tree (--root selects the package it imports)"""
@@ -187,14 +203,15 @@ def check_driver(args, arms):
     rows, differing = [], 0
     for arm, launch, dist in cases:
         extra = ["--check", "--launch", launch] + (["--dump-launches", args.dump_launches] if args.dump_launches else [])
-        got = {label: run_worker(label, root, arm, extra, {"CRIS_FORCE_DIST": "1" if dist else "0"}) for label, root in trees}
+        got = {label: run_worker(label, root, arm, extra, {"CRIS_FORCE_DIST": "1" if dist else "0"}) for label, root in trees
+               if knows(root, arm)}
         this = got["this"]
         assert this["force_dist"] == dist and (this["grad_exchange"] != "none") == dist and (not dist or this["exchanges"]["sum"] > 0), this
         same = {k: got["parent"].get(k) == this[k] for k in ("losses", "metrics", "state_sha256", "launches_sha256", "exchanges")
-                if this.get(k) is not None} if args.parent else {}
+                if this.get(k) is not None} if "parent" in got else {}
         differing += int(not all(same.values()))
         rows.append({"arm": arm + (" + CRIS_FORCE_DIST=1" if dist else ""), "launch": launch, "equal": same, **got})
-        print("%-30s %-8s %s  state %s  launches %s" % (rows[-1]["arm"], launch, " ".join("%s=%s" % kv for kv in same.items()) or "(no parent)",
+        print("%-30s %-8s %s  state %s  launches %s" % (rows[-1]["arm"], launch, " ".join("%s=%s" % kv for kv in same.items()) or "(no parent with this arm)",
                                                      this["state_sha256"][:12], (this.get("launches_sha256") or "-")[:12]), flush=True)
     if args.out:
         with open(args.out, "w") as f:
@@ -217,7 +234,7 @@ def table_md(summary):
 
 
 def time_driver(args, arms):
-    variants = [("parent:" + a, args.parent, a) for a in arms if args.parent] + [(a, HERE, a) for a in arms]
+    variants = [("parent:" + a, args.parent, a) for a in arms if args.parent and knows(args.parent, a)] + [(a, HERE, a) for a in arms]
     extra = ["--launch", "graph", "--steps", str(args.steps), "--windows", str(args.windows), "--warmup", str(args.warmup)]
     runs = {label: [] for label, _, _ in variants}
     for r in range(args.rounds):
@@ -230,7 +247,9 @@ def time_driver(args, arms):
                        "ms_per_step_runs": [x["ms_per_step"] for x in rs], "losses": sorted({x["loss"] for x in rs}),
                        "peak_allocated_mb": max(x["peak_allocated_mb"] for x in rs), "peak_reserved_mb": max(x["peak_reserved_mb"] for x in rs)}
                for label, rs in runs.items()}
-    for a in arms if args.parent else []:
+    for a in arms:
+        if "parent:" + a not in summary:
+            continue
         p, s = summary["parent:" + a], summary[a]
         spread, diff = max(p["ms_per_step_runs"]) - min(p["ms_per_step_runs"]), s["ms_per_step_median"] - p["ms_per_step_median"]
         s.update(parent_spread_ms=round(spread, 4), diff_ms_vs_parent=round(diff, 4), within_parent_spread=abs(diff) <= spread,
@@ -240,6 +259,11 @@ def time_driver(args, arms):
     if base is not None:                                 # what each arm costs on top of the plain step, and the plain step's own spread
         derived = {"baseline_spread_ms": round(max(base["ms_per_step_runs"]) - min(base["ms_per_step_runs"]), 4),
                    "cost_ms_vs_plain": {label: round(s["ms_per_step_median"] - base["ms_per_step_median"], 4) for label, s in summary.items()}}
+        if "plain" in summary and base is not summary["plain"]:          # and on top of THIS tree's plain step
+            own = summary["plain"]
+            derived.update(own_plain_spread_ms=round(max(own["ms_per_step_runs"]) - min(own["ms_per_step_runs"]), 4),
+                           cost_ms_vs_own_plain={label: round(s["ms_per_step_median"] - own["ms_per_step_median"], 4)
+                                                 for label, s in summary.items() if not label.startswith("parent:")})
     extras = {label: {k: rs[0][k] for k in ("ema_elements", "ema_buffer_mb", "skipped_elements", "bytes_per_update", "table_rows", "table_bytes",
                                             "launches_added", "descriptors", "grad_norm") if k in rs[0]} for label, rs in runs.items()}
     first = next(iter(runs.values()))[0]
