@@ -936,6 +936,7 @@ static int bn_bwd_reduce_launch(const cris_bn_bwd_params* pp, float* local_sums,
     CRIS_CHECK_ARG(p.dz && p.y && p.mean && p.invstd && p.sums && p.part, "null operand");
     CRIS_CHECK_ARG((p.C & 7) == 0 && p.C <= 8192, "C");
     CRIS_CHECK_ARG(!p.relu || p.pool || p.z || (p.scale && p.shift), "relu mask source");
+    CRIS_CHECK_ARG(!(p.relu && !p.pool && p.y2 && !p.z), "relu over two branches takes its mask from the stored output z");
     CRIS_CHECK_ARG(!p.pool || (p.scale && p.shift && !p.y2 && !p.mul), "pool backward needs scale/shift, plain BN");
     CRIS_CHECK_ARG(!p.mul || !p.dmul || (p.relu && !p.pool && !p.y2 && p.scale && p.shift && (p.lddz & 7) == 0 && (p.dz_coff & 7) == 0),
                    "multiplier gradient: plain BN + ReLU");
@@ -1122,6 +1123,7 @@ extern "C" int cris_bn_bwd_apply(const cris_bn_bwd_params* pp, void* stream) {
     const cris_bn_bwd_params& p = *pp;
     CRIS_CHECK_ARG(p.dz && p.y && p.mean && p.invstd && p.sums && p.scale && p.dy, "null operand");
     CRIS_CHECK_ARG((p.C & 7) == 0 && (p.lddy & 7) == 0 && (p.dy_coff & 7) == 0 && p.count > 0.f, "geometry");
+    CRIS_CHECK_ARG(!(p.relu && !p.pool && p.y2 && !p.z), "relu over two branches takes its mask from the stored output z");
     const long total = (long)p.Bn * p.H * p.W * (p.C >> 3);
     static const int use_fast = cris_env_int("CRIS_BN_APPLY_FAST", 1);
     const int cvs = bn_cv_shift(p.C);

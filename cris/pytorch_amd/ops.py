@@ -562,7 +562,10 @@ def bn_bwd(dz, y, scale, shift, mean, invstd, sums, dy, Bn, H, W, C_, count, *, 
            di_coff=0, dident_accum=False, between=None, link=None, local_sums=None, pre_reduced: Optional[BnrParts] = None):
     """reduce + apply.  `between(sums)` (optional) runs between the two launches (SyncBN all-reduce by a collective); with
     `link` (hip.P2PLink) the summation launch itself adds this rank's sums into `local_sums` and exchanges them
-    (cris_bn_bwd_reduce_sync): `sums` then receives the sums over all ranks."""
+    (cris_bn_bwd_reduce_sync): `sums` then receives the sums over all ranks.
+    ReLU mask: from the stored output `z` when it is given, else recomputed from scale * y + shift.  With a second branch
+    (`y2`) it cannot be recomputed from one branch, so `relu` with `y2` needs `z` (both launchers refuse the call otherwise);
+    `relu=False` with `y2` needs none."""
     p = hip.BnBwdParams()
     p.dz, p.lddz, p.dz_coff = ptr(dz), lddz if lddz is not None else dz.shape[-1], dz_coff
     if z is not None:
