@@ -1,5 +1,6 @@
 // Data-movement / elementwise / small reduction kernels of the CRIS path (all HBM- or latency-bound).
 // bf16 tensors are accessed as 16-byte vectors (8 channels per lane) wherever the layout allows.
+#include <cmath>
 #include "common.h"
 #include "../../../include/cris_hip.h"
 
@@ -877,6 +878,163 @@ __global__ void bce_bwd_kernel(const float* x, const float* t, long n, const flo
 extern "C" int cris_bce_bwd(const float* logits, const float* target, long n, const float* gscale, float* dlogits, void* stream) {
     CRIS_CHECK_ARG(logits && target && dlogits && n > 0, "bad args");
     hipLaunchKernelGGL(bce_bwd_kernel, dim3(cris_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, n, gscale, dlogits);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
+// Configurable segmentation loss: w_bce * BCE-with-logits(pos_weight = pw) + w_dice * soft Dice per sample (smooth s).
+//   forward, launch 1: block (k, b) reduces slice k of sample b - SEG_SLICES slices per sample, a compile-time constant, each a
+//     multiple of 4 elements long - into four partials (BCE term, p*t, p, t): fixed order inside the block (wave butterfly, then
+//     the waves in order), one float4 store per block;
+//   forward, launch 2: one wave adds each sample's slices in slice order (a sample per lane), writes coef[b] = (a_b, c_b), then
+//     lane 0 adds the samples in sample order: loss, terms = (bce, dice) unweighted.  No atomics anywhere.
+//   backward: dx = g * [w_bce/n * ((1 + (pw-1) t) p - pw t) + w_dice/B * p (1-p) (c_b - a_b t)].
+// A sample's row starts at element b*HW of a 16-byte-aligned operand, so off a 16-byte boundary whenever HW % 4 != 0: every slice
+// has a scalar head up to the next boundary, a float4 body and a scalar tail.  exp / log1p are the accurate ones (the gradient
+// of the Dice term is a difference of like terms; the loss is 0.1% of the step).
+#define SEG_SLICES 16
+struct seg_px { float p, q; };                            // sigmoid(v) and 1 - sigmoid(v), each from the small side
+__device__ __forceinline__ seg_px seg_sigmoid(float v, float e) {          // e = exp(-|v|) in [0, 1]
+    const float r = 1.f / (1.f + e);
+    seg_px o;
+    o.p = v >= 0.f ? r : e * r;
+    o.q = v >= 0.f ? e * r : r;
+    return o;
+}
+__device__ __forceinline__ void seg_acc(float v, float y, float pw, float& sb, float& si, float& sp, float& st) {
+    const float e = expf(-fabsf(v));
+    // (1 - t) x + (1 + (pw - 1) t) softplus(-x), softplus(-x) = max(-x, 0) + log1p(exp(-|x|))
+    sb += (1.f - y) * v + (1.f + (pw - 1.f) * y) * (fmaxf(-v, 0.f) + log1pf(e));
+    const float p = seg_sigmoid(v, e).p;
+    si += p * y;
+    sp += p;
+    st += y;
+}
+__global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float* x, const float* t, int Bn, int HW, float pw, float* part) {
+    __shared__ float sw[4][4];
+    const long per = (((long)HW + SEG_SLICES * 4 - 1) / (SEG_SLICES * 4)) * 4;          // slice length: a multiple of 4
+    for (int b = blockIdx.y; b < Bn; b += gridDim.y) {
+        const long lo = (long)blockIdx.x * per < HW ? (long)blockIdx.x * per : (long)HW, hi = lo + per < HW ? lo + per : (long)HW;
+        const long g0 = (long)b * HW + lo;                 // the slice's first element in the whole operand
+        const float* xs = x + g0;
+        const float* ts = t + g0;
+        const long len = hi - lo;
+        const long head = ((-g0) & 3) < len ? ((-g0) & 3) : len;          // elements before the next 16-byte boundary
+        const long n4 = (len - head) >> 2;
+        float sb = 0.f, si = 0.f, sp = 0.f, st = 0.f;
+        if ((long)threadIdx.x < head) seg_acc(xs[threadIdx.x], ts[threadIdx.x], pw, sb, si, sp, st);
+        for (long i = threadIdx.x; i < n4; i += 256) {
+            const float4 v = *reinterpret_cast<const float4*>(xs + head + i * 4);
+            const float4 y = *reinterpret_cast<const float4*>(ts + head + i * 4);
+            seg_acc(v.x, y.x, pw, sb, si, sp, st);
+            seg_acc(v.y, y.y, pw, sb, si, sp, st);
+            seg_acc(v.z, y.z, pw, sb, si, sp, st);
+            seg_acc(v.w, y.w, pw, sb, si, sp, st);
+        }
+        for (long i = head + n4 * 4 + threadIdx.x; i < len; i += 256) seg_acc(xs[i], ts[i], pw, sb, si, sp, st);
+        sb = wave_sum(sb);
+        si = wave_sum(si);
+        sp = wave_sum(sp);
+        st = wave_sum(st);
+        __syncthreads();                                   // the previous sample's table consumed
+        if ((threadIdx.x & 63) == 0) {
+            float* w = sw[threadIdx.x >> 6];
+            w[0] = sb; w[1] = si; w[2] = sp; w[3] = st;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float4 o;
+            o.x = (sw[0][0] + sw[1][0]) + (sw[2][0] + sw[3][0]);
+            o.y = (sw[0][1] + sw[1][1]) + (sw[2][1] + sw[3][1]);
+            o.z = (sw[0][2] + sw[1][2]) + (sw[2][2] + sw[3][2]);
+            o.w = (sw[0][3] + sw[1][3]) + (sw[2][3] + sw[3][3]);
+            *reinterpret_cast<float4*>(part + ((size_t)b * SEG_SLICES + blockIdx.x) * 4) = o;
+        }
+    }
+}
+__global__ __launch_bounds__(64) void seg_loss_finish_kernel(const float* part, int Bn, int HW, float w_bce, float w_dice, float s,
+                                                             float* loss, float* terms, float* coef) {
+    __shared__ float sbce[64], sdice[64];
+    float bce = 0.f, dice = 0.f;                           // lane 0's running sums over the samples
+    for (int base = 0; base < Bn; base += 64) {
+        const int b = base + threadIdx.x;
+        if (b < Bn) {
+            float ab = 0.f, ai = 0.f, ap = 0.f, at = 0.f;
+            for (int k = 0; k < SEG_SLICES; ++k) {         // slice order
+                const float4 q = *reinterpret_cast<const float4*>(part + ((size_t)b * SEG_SLICES + k) * 4);
+                ab += q.x; ai += q.y; ap += q.z; at += q.w;
+            }
+            const float D = ap + at + s, num = 2.f * ai + s;
+            coef[(size_t)b * 2] = 2.f / D;
+            coef[(size_t)b * 2 + 1] = num / (D * D);
+            sbce[threadIdx.x] = ab;
+            sdice[threadIdx.x] = 1.f - num / D;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int m = Bn - base < 64 ? Bn - base : 64;
+            for (int j = 0; j < m; ++j) { bce += sbce[j]; dice += sdice[j]; }          // sample order
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        bce /= (float)((long)Bn * HW);
+        dice /= (float)Bn;
+        terms[0] = bce;
+        terms[1] = dice;
+        loss[0] = w_bce * bce + w_dice * dice;
+    }
+}
+__global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* x, const float* t, int Bn, int HW, float w_bce, float w_dice,
+                                                           float pw, const float* coef, const float* gscale, float* dx) {
+    const float g = gscale ? gscale[0] : 1.f;
+    const float kb = g * w_bce / (float)((long)Bn * HW), kd = g * w_dice / (float)Bn;
+    for (int b = blockIdx.y; b < Bn; b += gridDim.y) {
+        const float a = coef[(size_t)b * 2], c = coef[(size_t)b * 2 + 1];
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long)gridDim.x * 256) {
+            const size_t o = (size_t)b * HW + i;
+            const float v = x[o], y = t[o];
+            const seg_px s = seg_sigmoid(v, expf(-fabsf(v)));
+            dx[o] = kb * ((1.f + (pw - 1.f) * y) * s.p - pw * y) + kd * (s.p * s.q * (c - a * y));
+        }
+    }
+}
+#define SEG_MAX_GRID_Y 65535
+static int seg_loss_check_config(const char* fn, float w_bce, float w_dice, float pw, float s) {
+    const char* msg = !(std::isfinite(w_bce) && std::isfinite(w_dice) && std::isfinite(pw) && std::isfinite(s)) ? "w_bce, w_dice, pw and s must be finite"
+                      : (w_bce < 0.f || w_dice < 0.f)  ? "w_bce and w_dice must be >= 0"
+                      : (w_bce == 0.f && w_dice == 0.f) ? "w_bce and w_dice must not both be 0"
+                      : !(pw > 0.f)                     ? "pw must be > 0"
+                      : !(s > 0.f)                      ? "s must be > 0"
+                                                        : nullptr;
+    if (msg) {
+        cris_set_error("%s: %s", fn, msg);
+        return -1;
+    }
+    return 0;
+}
+extern "C" long cris_seg_loss_ws_floats(int Bn) { return Bn < 1 ? 0 : (long)Bn * SEG_SLICES * 4; }
+extern "C" int cris_seg_loss_fwd(const float* logits, const float* target, int Bn, int HW, float w_bce, float w_dice, float pw, float s,
+                                 float* loss, float* terms, float* coef, float* ws, void* stream) {
+    CRIS_CHECK_ARG(logits && target && loss && terms && coef && ws, "null operand");
+    CRIS_CHECK_ARG(Bn >= 1, "Bn must be >= 1");
+    CRIS_CHECK_ARG(HW >= 1, "HW must be >= 1");
+    if (seg_loss_check_config(__func__, w_bce, w_dice, pw, s)) return -1;
+    CRIS_CHECK_ARG((uintptr_t)logits % 16 == 0 && (uintptr_t)target % 16 == 0 && (uintptr_t)ws % 16 == 0, "operands must be 16-byte aligned");
+    hipLaunchKernelGGL(seg_loss_fwd_kernel, dim3(SEG_SLICES, Bn < SEG_MAX_GRID_Y ? Bn : SEG_MAX_GRID_Y), dim3(256), 0, (hipStream_t)stream,
+                       logits, target, Bn, HW, pw, ws);
+    hipLaunchKernelGGL(seg_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ws, Bn, HW, w_bce, w_dice, s, loss, terms, coef);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int cris_seg_loss_bwd(const float* logits, const float* target, int Bn, int HW, float w_bce, float w_dice, float pw, float s,
+                                 const float* coef, const float* gscale, float* dlogits, void* stream) {
+    CRIS_CHECK_ARG(logits && target && coef && dlogits, "null operand");
+    CRIS_CHECK_ARG(Bn >= 1, "Bn must be >= 1");
+    CRIS_CHECK_ARG(HW >= 1, "HW must be >= 1");
+    if (seg_loss_check_config(__func__, w_bce, w_dice, pw, s)) return -1;
+    hipLaunchKernelGGL(seg_loss_bwd_kernel, dim3(cris_grid_1d(HW, 256, 1024), Bn < SEG_MAX_GRID_Y ? Bn : SEG_MAX_GRID_Y), dim3(256), 0,
+                       (hipStream_t)stream, logits, target, Bn, HW, w_bce, w_dice, pw, coef, gscale, dlogits);
     CRIS_LAUNCH_CHECK();
     return 0;
 }

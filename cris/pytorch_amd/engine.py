@@ -119,6 +119,10 @@ class Engine:
         self.training = True
         self.seed = 0
         self.seed_dev = None            # optional device word added to every dropout seed (graph replay: trainer.py)
+        # the loss of the training forward: None = mean BCE with logits (cris_bce_fwd / cris_bce_bwd, the reference's), or an
+        # ops.SegLoss (weighted BCE + soft Dice: cris_seg_loss_fwd / cris_seg_loss_bwd) - set_loss
+        self.loss_spec = None
+        self.loss_terms = None          # device [2]: the unweighted (bce, dice) of the last training forward under a SegLoss
         # the text encoder (12 layers of M = B*L ~ 136-row GEMMs: latency-bound, ~16 workgroups each) is independent of
         # the visual encoder until the neck: it runs on a second HIP stream, forward and backward, underneath the convs
         self.side = torch.cuda.Stream(device=device) if torch.device(device).type == "cuda" else None
@@ -1083,6 +1087,12 @@ class Engine:
                              % (word.shape[1], self.P["backbone.positional_embedding"].shape[0]))
         return word
 
+    def set_loss(self, spec):
+        """the loss of the training forwards from now on: None (or an ops.SegLoss equal to the defaults) = the reference's mean BCE
+        with logits, else the ops.SegLoss.  It is an argument of launches: a captured / recorded step has to be built again."""
+        self.loss_spec = ops.SegLoss.normalized(spec)
+        self.loss_terms = None
+
     def forward(self, img, word, mask=None, training=True, seed=0, taps: Optional[dict] = None):
         word = self._begin_forward(word, training, seed)
         main = torch.cuda.current_stream()
@@ -1122,12 +1132,20 @@ class Engine:
         msk = self.empty(B, 1, OH, OW, dtype=F32)
         ops.mask_resize_nearest(mask.contiguous().float(), OH, OW, msk)
         loss = self.empty(1, dtype=F32)
-        ops.bce_fwd(pred, msk, loss)
+        spec = self.loss_spec
+        if spec is None:
+            ops.bce_fwd(pred, msk, loss)
+        else:
+            self.loss_terms, coef = self.empty(2, dtype=F32), self.empty(B, 2, dtype=F32)
+            ops.seg_loss_fwd(pred, msk, spec, loss, self.loss_terms, coef)
         c = self.head.vis_dim // 2
 
         def bwd_loss():
             dpred = self.empty(B, 1, OH, OW, dtype=F32)
-            ops.bce_bwd(pred, msk, self._gscale, dpred)
+            if spec is None:
+                ops.bce_bwd(pred, msk, self._gscale, dpred)
+            else:
+                ops.seg_loss_bwd(pred, msk, spec, coef, self._gscale, dpred)
             gx, acc = x.grad_target()
             assert not acc
             self._dwb = self.zeros(B, wb.ld)

@@ -346,6 +346,9 @@ _SIGS = {
     "cris_bce_fwd": (I, [P, P, L, P, P, P]),
     "cris_bce_ws_floats": (I, []),
     "cris_bce_bwd": (I, [P, P, L, P, P, P]),
+    "cris_seg_loss_fwd": (I, [P, P, I, I, F, F, F, F, P, P, P, P, P]),
+    "cris_seg_loss_ws_floats": (L, [I]),
+    "cris_seg_loss_bwd": (I, [P, P, I, I, F, F, F, F, P, P, P, P]),
     "cris_train_metric": (I, [P, P, I, I, F, F, P, P]),
     "cris_sigmoid_bicubic_up": (I, [P, I, I, I, I, I, P, P]),
     "cris_warp_affine_cubic": (I, [P, I, I, P, I, I, F, P, P]),

@@ -1,7 +1,8 @@
 """`CRIS` - drop-in for the reference's `model.segmenter.CRIS` (reference model/segmenter.py:10-62) on the HIP path.
 
 Same constructor (`CRIS(cfg)` reading clip_pretrain, word_len, fpn_in, fpn_out, num_layers, vis_dim, num_head, dim_ffn,
-dropout, intermediate, word_dim), same `forward(img, word, mask=None)` contract - train mode returns
+dropout, intermediate, word_dim; and, optionally, loss_bce_weight, loss_dice_weight, loss_pos_weight, loss_dice_smooth -
+seg_loss_from_cfg), same `forward(img, word, mask=None)` contract - train mode returns
 `(pred.detach(), mask_resized, loss)`, eval mode `pred.detach()` - same parameter / buffer names and shapes, so the
 reference's `train.py` / `engine/engine.py` drive it unchanged: `.cuda()`, `.train()/.eval()`, `state_dict()` /
 `load_state_dict()` (checkpoint interchange), `nn.SyncBatchNorm.convert_sync_batchnorm`, `DistributedDataParallel(...,
@@ -43,6 +44,15 @@ def head_spec_from_cfg(cfg) -> arch.HeadSpec:
                          vis_dim=int(_cfg_get(cfg, "vis_dim")), num_head=int(_cfg_get(cfg, "num_head")),
                          dim_ffn=int(_cfg_get(cfg, "dim_ffn")), dropout=float(_cfg_get(cfg, "dropout")),
                          intermediate=bool(_cfg_get(cfg, "intermediate", False)), word_dim=int(_cfg_get(cfg, "word_dim")))
+
+
+def seg_loss_from_cfg(cfg):
+    """The training loss a config asks for: the optional keys loss_bce_weight, loss_dice_weight, loss_pos_weight and
+    loss_dice_smooth make an ops.SegLoss (weighted BCE + soft Dice, Engine.set_loss); a config without them - every shipped
+    yaml - or with the default values gives None, the reference's mean BCE with logits (model/segmenter.py:59)."""
+    keys = dict(loss_bce_weight="bce_weight", loss_dice_weight="dice_weight", loss_pos_weight="pos_weight", loss_dice_smooth="dice_smooth")
+    given = {field: _cfg_get(cfg, key) for key, field in keys.items() if _cfg_get(cfg, key) is not None}
+    return ops.SegLoss.normalized(ops.SegLoss(**given)) if given else None
 
 
 def load_clip_state_dict(path):
@@ -166,6 +176,7 @@ class CRIS(nn.Module):
         clip_sd = load_clip_state_dict(_cfg_get(cfg, "clip_pretrain"))
         self.clip_spec = arch.clip_spec_from_state_dict(clip_sd)
         self.head_spec = head_spec_from_cfg(cfg)
+        self.loss_spec = seg_loss_from_cfg(cfg)          # None: the reference's loss; fixed for the life of the module
         tree = arch.build_param_tree(self.clip_spec, self.head_spec)
         # Vision & Text Encoder (model/segmenter.py:13-16), Multi-Modal FPN (:18), Decoder (:20-25), Projector (:27)
         self.backbone, self.neck, self.decoder, self.proj = tree.backbone, tree.neck, tree.decoder, tree.proj
@@ -347,6 +358,7 @@ class CRIS(nn.Module):
             from ..dist import TorchDistComm
             comm = TorchDistComm(device)
         self._engine = Engine(self.clip_spec, self.head_spec, params, buffers, device, comm=comm, sync_bn=sync)
+        self._engine.set_loss(self.loss_spec)
         self._engine_key = key
         # SyncBN statistics (142 exchanges of a few KB per step, all on the critical path): through the peer-mapped mailboxes,
         # inside the BatchNorm launches, as under NativeTrainer - when allocation, IPC mapping and a self-test with known data

@@ -920,6 +920,60 @@ def bce_bwd(logits, target, gscale, dlogits):
     hip.call("cris_bce_bwd", ptr(logits), ptr(target), logits.numel(), ptr(gscale), ptr(dlogits), _stream())
 
 
+@dataclass(frozen=True)
+class SegLoss:
+    """loss = bce_weight * BCE-with-logits(pos_weight) + dice_weight * soft Dice per sample (dice_smooth in numerator and
+    denominator) - include/cris_hip.h cris_seg_loss_fwd.  The defaults are the reference's mean BCE (model/segmenter.py:59).
+    Validated here, before a device is touched."""
+    bce_weight: float = 1.0
+    dice_weight: float = 0.0
+    pos_weight: float = 1.0
+    dice_smooth: float = 1.0
+
+    def __post_init__(self):
+        for f in ("bce_weight", "dice_weight", "pos_weight", "dice_smooth"):
+            v = getattr(self, f)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError("SegLoss.%s must be a finite number, got %r" % (f, v))
+            object.__setattr__(self, f, float(v))
+        if self.bce_weight < 0 or self.dice_weight < 0:
+            raise ValueError("SegLoss: bce_weight and dice_weight must be >= 0, got %r and %r" % (self.bce_weight, self.dice_weight))
+        if self.bce_weight == 0 and self.dice_weight == 0:
+            raise ValueError("SegLoss: bce_weight and dice_weight must not both be 0")
+        if not self.pos_weight > 0:
+            raise ValueError("SegLoss.pos_weight must be > 0, got %r" % (self.pos_weight,))
+        if not self.dice_smooth > 0:
+            raise ValueError("SegLoss.dice_smooth must be > 0, got %r" % (self.dice_smooth,))
+
+    @property
+    def scalars(self):
+        """(w_bce, w_dice, pw, s): the four float arguments of the launches"""
+        return self.bce_weight, self.dice_weight, self.pos_weight, self.dice_smooth
+
+    @staticmethod
+    def normalized(spec) -> Optional[SegLoss]:
+        """None for None and for a spec equal to the defaults (the cris_bce_fwd / cris_bce_bwd path, as always); else the spec"""
+        if spec is None:
+            return None
+        if not isinstance(spec, SegLoss):
+            raise ValueError("loss must be None or an ops.SegLoss, got %r" % (spec,))
+        return None if spec == SegLoss() else spec
+
+
+def seg_loss_fwd(logits, target, spec: SegLoss, loss, terms, coef):
+    """logits, target [B, ...] fp32 contiguous; loss [1], terms [2], coef [B, 2] are overwritten"""
+    Bn = logits.shape[0]
+    ws = torch.empty(hip.load().cris_seg_loss_ws_floats(Bn), dtype=torch.float32, device=logits.device)
+    hip.call("cris_seg_loss_fwd", ptr(logits), ptr(target), Bn, logits.numel() // Bn, *spec.scalars, ptr(loss), ptr(terms), ptr(coef),
+             ptr(ws), _stream())
+
+
+def seg_loss_bwd(logits, target, spec: SegLoss, coef, gscale, dlogits):
+    Bn = logits.shape[0]
+    hip.call("cris_seg_loss_bwd", ptr(logits), ptr(target), Bn, logits.numel() // Bn, *spec.scalars, ptr(coef), ptr(gscale), ptr(dlogits),
+             _stream())
+
+
 def train_metric(logits, target, Bn, HW, out, thr=0.35, pr_iou=0.5):
     hip.call("cris_train_metric", ptr(logits), ptr(target), Bn, HW, float(thr), float(pr_iou), ptr(out), _stream())
 

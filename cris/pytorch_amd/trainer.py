@@ -49,6 +49,13 @@ the `backbone_no_decay` group model/__init__.py:4-29 keeps commented out) are re
 `cris_adamw_step`, which reads one decay per tensor from a small device array: the same two launches, once per optimizer step,
 independent of clipping (the norm is the raw gradient's), no communication.  With the defaults the step issues the launches it
 always did - `cris_adam_step_amp` with the scalar - and nothing is allocated.
+
+Loss (`loss=ops.SegLoss(...)`): bce_weight * BCE-with-logits(pos_weight) + dice_weight * soft Dice per sample, computed and
+differentiated on the device by `cris_seg_loss_fwd` / `cris_seg_loss_bwd` in the place of `cris_bce_fwd` / `cris_bce_bwd`: two
+forward launches and one backward launch, as before, inside the captured / recorded step.  The Dice term is a mean of per-sample
+values, so it is exact under data parallelism and under accum_steps.  `loss_terms` holds the unweighted (bce, dice) of the step.
+No communication; configuration like the schedule table, not part of optimizer_state_dict().  With loss=None (the default, and any
+SegLoss equal to the defaults) the step issues the launches it always did and nothing is allocated.
 """
 import contextlib
 import os
@@ -120,8 +127,10 @@ class NativeTrainer:
     def __init__(self, clip: ClipSpec, head: HeadSpec, state_dict, device, base_lr=1e-4, lr_multi=0.1, weight_decay=0.0,
                  comm=None, sync_bn=False, use_graph: Optional[bool] = None, launch: Optional[str] = None, max_norm: float = 0.0,
                  track_grad_norm: bool = False, accum_steps: int = 1, ema_decay: Optional[float] = None, ema_every: int = 1,
-                 ema_warmup: bool = False, lr_schedule=None, decoupled_weight_decay: bool = False, no_decay=None):
-        """weight_decay = w >= 0: coupled L2 on every tensor (the reference's Adam); decoupled_weight_decay: AdamW's p *= 1 - lr * w
+                 ema_warmup: bool = False, lr_schedule=None, decoupled_weight_decay: bool = False, no_decay=None, loss=None):
+        """loss = None: the reference's mean BCE with logits; an ops.SegLoss: weighted BCE + soft Dice on the device (the module
+        docstring; set_loss; loss_terms).
+        weight_decay = w >= 0: coupled L2 on every tensor (the reference's Adam); decoupled_weight_decay: AdamW's p *= 1 - lr * w
         instead; no_decay: None or a rule (name, tensor) -> bool, True = this tensor's decay is 0 (no_decay_1d,
         no_decay_1d_and_positional) - the module docstring; set_weight_decay; weight_decays.
         lr_schedule = array-like [n_steps, 2]: the (backbone, rest) learning rates of every optimizer step, followed on the device
@@ -137,6 +146,7 @@ class NativeTrainer:
         ema_cfg = self._checked_ema(ema_decay, ema_every, ema_warmup)
         lr_schedule = self._checked_schedule(lr_schedule)
         decay_cfg = self._checked_weight_decay(weight_decay, decoupled_weight_decay, no_decay)
+        loss = ops.SegLoss.normalized(loss)
         if no_decay is not None:                 # (the rule's answers are checked on the tensors as given, before a device is touched)
             self._exempt(no_decay, [(k, v) for k, v in strip_ddp_prefix(state_dict).items()
                                     if v.is_floating_point() and not k.endswith(("running_mean", "running_var"))])
@@ -221,8 +231,9 @@ class NativeTrainer:
         self._static = None
         self.graph_error = None
         self._host_steps = 0
-        self._acc = self._loss_acc = self._metric_micro = None
+        self._acc = self._loss_acc = self._metric_micro = self._terms_acc = None
         self.set_accum_steps(self.accum_steps)
+        self.set_loss(loss)
         self._ema = None
         self.set_ema(*ema_cfg)                   # (after the rank-0 broadcast above: the average starts from the shared values)
         self._lr = None
@@ -283,7 +294,37 @@ class NativeTrainer:
                 self._metric_micro = torch.zeros(2, device=self.device)
         else:
             self._acc = self._loss_acc = self._metric_micro = None
+        self._size_terms_acc()
         self._invalidate()
+
+    def set_loss(self, spec):
+        """the loss from now on: None (or an ops.SegLoss equal to the defaults) = the reference's mean BCE with logits, else the
+        ops.SegLoss (weighted BCE + soft Dice).  Its scalars are arguments of launches, so the step is captured / recorded again.
+        Configuration, like the schedule table: not written into optimizer_state_dict() and not restored."""
+        self.engine.set_loss(spec)
+        self._size_terms_acc()
+        self._invalidate()
+
+    def _size_terms_acc(self):
+        """the running mean of the micro-batches' loss terms: held only with a SegLoss AND accum_steps > 1"""
+        if self.engine.loss_spec is not None and self.accum_steps > 1:
+            if self._terms_acc is None:
+                self._terms_acc = torch.zeros(2, device=self.device)
+        else:
+            self._terms_acc = None
+
+    @property
+    def loss_spec(self):
+        return self.engine.loss_spec
+
+    @property
+    def loss_terms(self):
+        """the unweighted (bce, dice) of the last step under a SegLoss: a device tensor [2] written by the step itself (no sync
+        here), overwritten by the next step; with accum_steps = K > 1 the mean over the K micro-batches.  None with the default
+        loss, and before the first step."""
+        if self.engine.loss_spec is None:
+            return None
+        return self._terms_acc if self.accum_steps > 1 else self.engine.loss_terms
 
     @staticmethod
     def _checked_ema(decay, every, warmup):
@@ -421,6 +462,8 @@ class NativeTrainer:
         if K > 1:
             ops.zero_(self._loss_acc)
             ops.zero_(self.metric)
+            if self._terms_acc is not None:
+                ops.zero_(self._terms_acc)
         for m in range(K):
             if K == 1:
                 ops.step_advance(self.step_dev, self.seed_dev, self.xgen_dev)
@@ -435,6 +478,8 @@ class NativeTrainer:
             pred, msk, loss = e.forward(*micro, training=True, seed=seed)
             if K > 1:
                 ops.axpy_f32(self._loss_acc, loss, 1.0 / K)
+                if self._terms_acc is not None:
+                    ops.axpy_f32(self._terms_acc, e.loss_terms, 1.0 / K)
             self._metric(pred, msk)
             e.backward(on_stage_done=self._stage_hook(m))
         if self._exchanges():

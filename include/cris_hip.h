@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -477,6 +477,20 @@ int cris_mask_resize_nearest(const float* mask, int Bn, int IH, int IW, int OH, 
 int cris_bce_fwd(const float* logits, const float* target, long n, float* loss, float* ws, void* stream);
 int cris_bce_ws_floats(void);
 int cris_bce_bwd(const float* logits, const float* target, long n, const float* gscale, float* dlogits, void* stream);
+/* Configurable segmentation loss on logits / target [Bn][HW] (n = Bn * HW, p = sigmoid(x), targets anywhere in [0, 1]):
+ *   bce  = 1/n sum_b sum_i (1 - t) x + (1 + (pw - 1) t) softplus(-x)      (torch's BCEWithLogitsLoss with pos_weight = pw)
+ *   dice = 1/Bn sum_b 1 - (2 I_b + s) / (P_b + T_b + s),  I_b = sum_i p t, P_b = sum_i p, T_b = sum_i t    (per sample)
+ *   loss[0] = w_bce * bce + w_dice * dice ; terms[2] = (bce, dice) unweighted ; coef[Bn][2] = (a_b, c_b) = (2 / D_b, (2 I_b + s) / D_b^2),
+ *   D_b = P_b + T_b + s, for the backward.  Two launches: 16 blocks per sample write four partials each into ws
+ *   [cris_seg_loss_ws_floats(Bn)], one wave adds them in slice order, then the samples in sample order: no atomics, the same bits
+ *   on every run and for every grid.  logits, target and ws 16-byte aligned; any HW >= 1, Bn >= 1.
+ *   dlogits = (*gscale or 1) * [ w_bce / n * ((1 + (pw - 1) t) p - pw t) + w_dice / Bn * p (1 - p) (c_b - a_b t) ]     (one launch)
+ * w_bce, w_dice >= 0 and not both 0, pw > 0, s > 0, all finite: refused before any launch otherwise. */
+int cris_seg_loss_fwd(const float* logits, const float* target, int Bn, int HW, float w_bce, float w_dice, float pw, float s,
+                      float* loss, float* terms, float* coef, float* ws, void* stream);
+long cris_seg_loss_ws_floats(int Bn);
+int cris_seg_loss_bwd(const float* logits, const float* target, int Bn, int HW, float w_bce, float w_dice, float pw, float s,
+                      const float* coef, const float* gscale, float* dlogits, void* stream);
 /* trainMetricGPU (utils/misc.py:114-129): out[0] = 100*mean IoU, out[1] = 100*mean(IoU > pr_iou) */
 int cris_train_metric(const float* logits, const float* target, int Bn, int HW, float thr, float pr_iou, float* out,
                       void* stream);

@@ -1,20 +1,20 @@
 """What the options of NativeTrainer cost per train step, and the proof that a change of the trainer changed nothing.
 
-Timing (profiles/grad_clip.md, grad_accum.md, ema.md, lr_schedule.md, trainer_refactor.md, adamw.md): the trainer at BASELINE.json configs[1]
+Timing (profiles/grad_clip.md, grad_accum.md, ema.md, lr_schedule.md, trainer_refactor.md, adamw.md, seg_loss.md): the trainer at BASELINE.json configs[1]
 (R50, 416 x 416, micro-batch 8, one GPU, the whole optimizer step as one captured graph), one ARM per row of the table below, each
 timed in fresh processes that alternate between the arms - and, with --parent DIR, the same arms run from a built checkout of the
 commit to compare against - so that drift of the machine lands on all of them alike.  Each process warms up, then times `--windows`
 windows of `--steps` micro-batches with a host clock around a device synchronise and reports the median window and the peak device
 memory of the torch allocator.  An arm of this tree is judged against the parent's arm of the same name: its median has to lie
 within the parent processes' own spread (max - min) of the parent's median.  An arm whose constructor arguments the parent's
-trainer does not know (adamw, adamw_schedule against a commit before them) runs from this tree only.
+trainer does not know (adamw, adamw_schedule, dice against a commit before them) runs from this tree only.
     python tools/trainer_bench.py [--arms plain,schedule,all] [--parent ../parent-checkout] --rounds 4 [--out result.json] [--md table.md]
 
 --check: every arm in each of the launch modes eager / graph / cmdlist, and `plain` and `all` once more with CRIS_FORCE_DIST=1 (the
 exchange branch of the stage hooks, through a one-rank communicator that counts the exchanges), on the tiny spec at 64 x 64: four
 steps from synthetic_state_dict(..., 0) on synth.make_batch(..., t).  A process prints the losses and metrics as hex floats, a
 sha256 of the state the steps left behind (parameters, BatchNorm buffers, Adam moments, the step / seed / generation counters, the
-average and its state record, the rates of the last step) and, for cmdlist, a sha256 of the recorded list (every entry's name and
+average and its state record, the rates of the last step, the loss terms of the last step) and, for cmdlist, a sha256 of the recorded list (every entry's name and
 its non-pointer arguments; --dump-launches DIR writes the text).  With --parent the run fails unless all of them are equal,
 exactly, between the two trees.
     python tools/trainer_bench.py --check --parent ../parent-checkout [--out result.json]
@@ -25,6 +25,7 @@ import argparse
 import hashlib
 import json
 import os
+import re
 import statistics
 import subprocess
 import sys
@@ -46,6 +47,8 @@ ARMS = {                                                  # name -> constructor 
     # is compared with parents that do not have them)
     "adamw": {"weight_decay": 0.01, "decoupled_weight_decay": True, "no_decay": NO_DECAY},
     "adamw_schedule": {"weight_decay": 0.01, "decoupled_weight_decay": True, "no_decay": NO_DECAY, "lr_schedule": SCHEDULE},
+    # BCE + soft Dice: cris_seg_loss_fwd / cris_seg_loss_bwd in the place of cris_bce_fwd / cris_bce_bwd, the same number of launches
+    "dice": {"loss": {"dice_weight": 1.0}},               # (the fields of an ops.SegLoss of the package under --root: the worker builds it)
 }
 CHECK_MAX_NORM = 1e-3                                     # --check: far below the tiny spec's gradient norm, so that it does clip
 CHECK_STEPS = 4                                           # eager, capture / recording, two replays
@@ -76,13 +79,15 @@ def make_trainer(args, spec, n_steps):
     """(trainer, head, K, the schedule's table or None) of args.arm, from the package under args.root"""
     sys.path.insert(0, os.path.abspath(args.root))
     import torch
-    from cris.pytorch_amd import arch, debug, lr
+    from cris.pytorch_amd import arch, debug, lr, ops
     from cris.pytorch_amd.engine import Comm
     from cris.pytorch_amd import trainer
     from cris.pytorch_amd.trainer import NativeTrainer
     kw, table = dict(ARMS[args.arm]), None
     if "no_decay" in kw:
         kw["no_decay"] = getattr(trainer, kw["no_decay"])
+    if "loss" in kw:
+        kw["loss"] = ops.SegLoss(**kw["loss"])
     if "lr_schedule" in kw:
         kw["lr_schedule"] = table = lr.with_warmup(lr.cosine([1e-5, 1e-4], n_steps), max(n_steps // 10, 1), 0.01)
     if args.check and "max_norm" in kw:
@@ -126,6 +131,11 @@ def time_worker(args):
         skipped = sum(int((live == 0).sum()) * ema.views[name].shape[1] for name, live in ema.row_live.items())
         res.update(ema_elements=n, ema_buffer_mb=round(ema.flat.numel() * 4 / 2 ** 20, 1), skipped_elements=skipped,
                    bytes_per_update=12 * (n - skipped), ema_updates=tr.ema_num_updates)
+    if getattr(tr, "loss_terms", None) is not None:      # the loss is the weighted sum of the terms the step reports
+        res["loss_terms"] = [float(x) for x in tr.loss_terms.cpu()]
+        spec = tr.loss_spec
+        want = spec.bce_weight * res["loss_terms"][0] + spec.dice_weight * res["loss_terms"][1]
+        assert abs(res["loss"] - want) <= 1e-5 * max(1.0, abs(want)), (res["loss"], res["loss_terms"])
     if table is not None:                                # the last step used the row it should have
         last = tr.current_lrs.cpu().numpy()
         assert np.array_equal(last, table[tr.step_idx - 1]), (last, table[tr.step_idx - 1])
@@ -162,6 +172,8 @@ def check_worker(args):
         state += [tr._ema.flat, tr._ema.state]
     if tr._lr is not None:
         state.append(tr.current_lrs)
+    if getattr(tr, "loss_terms", None) is not None:
+        state.append(tr.loss_terms)
     h = hashlib.sha256()
     for t in state:
         h.update(t.detach().contiguous().reshape(-1).view(torch.uint8).cpu().numpy().tobytes())
@@ -179,10 +191,12 @@ def check_worker(args):
 
 
 def knows(root, arm):
-    """does the trainer of the tree at `root` take every constructor argument of `arm`?  (read from its source: no import)"""
+    """does the trainer of the tree at `root` take every constructor argument of `arm`?  (read from the constructor's parameter
+    list in its source: no import)"""
     with open(os.path.join(root, "cris", "pytorch_amd", "trainer.py")) as f:
         src = f.read()
-    return all(k in src for k in ARMS[arm])
+    sig = re.search(r"class NativeTrainer:.*?def __init__\((.*?)\):\n", src, flags=re.S).group(1)
+    return all(re.search(r"\b%s\b" % k, sig) for k in ARMS[arm])
 
 
 def run_worker(label, root, arm, extra=(), env=None):
