@@ -15,6 +15,7 @@ read by the standard library since Python 3.8).  `LmdbRecords` opens the LMDB en
 'val' (first sentence, image + tokens + params), 'test' (image + params with every sentence).
 """
 import pickle
+import re
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -88,27 +89,54 @@ class LmdbRecords:
         self.__init__(st["path"])
 
 
+_LEFT_RIGHT = re.compile(r"\b(left|right)", re.IGNORECASE)
+
+
+def swap_left_right(sentence: str) -> str:
+    """the sentence of a horizontally mirrored sample: `left` and `right` exchanged wherever a word starts with one of them, in
+    any letter case (`leftmost`, `right-hand`; not `bright`); the replacement is lower case.  A heuristic: it knows nothing of
+    `clockwise`, `3 o'clock`, `west` or `turn right`."""
+    return _LEFT_RIGHT.sub(lambda m: "right" if m.group(1).lower() == "left" else "left", sentence)
+
+
 class RecordPipeline:
     def __init__(self, input_size: int, word_length: int, device, mode: str = "train", tokenizer: Optional[BPETokenizer] = None,
-                 mask_dir: str = "", decode_threads: Optional[int] = None):
+                 mask_dir: str = "", decode_threads: Optional[int] = None, augment: Optional[inputpipe.Augment] = None):
         assert mode in ("train", "val", "test")
+        self.augment = inputpipe.Augment.normalized(augment)          # None = the reference's fixed letter-box and colours
+        if self.augment is not None and mode != "train":
+            raise ValueError("augment is for mode='train' only, got mode=%r" % (mode,))
         self.mode, self.word_length, self.device, self.mask_dir = mode, word_length, torch.device(device), mask_dir
         self.pre = inputpipe.Preprocessor((input_size, input_size), device)
         self.tok = tokenizer if tokenizer is not None else BPETokenizer()
         self.threads = decode_threads
+        self.last_augment = None
 
     def __call__(self, records: Sequence[dict], rng: Optional[np.random.Generator] = None):
         """train: (img [B,3,S,S] f32 cuda, word [B,L] i64 cuda, mask [B,S,S] f32 cuda)  - what engine.train's loop body gets after
         its .cuda() calls (engine/engine.py:39-42 adds the mask's channel dimension itself);
-        val:   (img, word, params) ; test: (img, params) with params as lists of per-sample dicts keyed like the reference's."""
+        val:   (img, word, params) ; test: (img, params) with params as lists of per-sample dicts keyed like the reference's.
+        With `augment`, one `rng.random((B, 8))` is drawn before the sentence draws (none without it: the random stream of an
+        un-augmented pipeline is what it always was), image and mask are warped and coloured by inputpipe.augment_params of
+        it, a mirrored sample's sentence goes through swap_left_right, and `last_augment` keeps the per-sample parameters with
+        the matrix used (host side; feeding them to `self.pre` reproduces the batch)."""
         rng = rng if rng is not None else np.random.default_rng()
+        params = None
+        if self.augment is not None:
+            params = inputpipe.augment_params(self.augment, rng.random((len(records), 8)), self.pre.input_size)
         images = jpegdec.decode_batch([r["img"] for r in records], self.device, threads=self.threads)
         masks = [pngdec.decode_gray(r["mask"]) for r in records] if self.mode == "train" else None
-        img, mask, _, invs = self.pre(images, masks)
+        if params is None:
+            img, mask, _, invs = self.pre(images, masks)
+        else:
+            img, mask, _, invs = self.pre(images, masks, params)
+            self.last_augment = self.pre.last_params
         if self.mode == "test":
             return img, [self._params(r, im, inv, test=True) for r, im, inv in zip(records, images, invs)]
         if self.mode == "train":
             sents = [r["sents"][int(rng.integers(r["num_sents"]))] for r in records]      # np.random.choice(num_sents)
+            if params is not None:
+                sents = [swap_left_right(s) if p.flip else s for s, p in zip(sents, params)]
         else:
             sents = [r["sents"][0] for r in records]
         word = self.tok.tokenize(sents, self.word_length, True).to(self.device, non_blocking=True)

@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it) */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -539,6 +539,34 @@ typedef struct { unsigned char v[4]; } cris_u8x4;
 int cris_preprocess_batch(const cris_sample_desc* samples_dev, int n, int S_h, int S_w, const short* tab_linear, const short* tab_cubic,
                           const float* lut_img, const float* lut_mask, const unsigned char* border_rgb /* host, 3 bytes */,
                           float* img_out, float* mask_out, void* stream);
+/* ---- training-time augmentation of the same launch (no reference counterpart: RefDataset has none; DESIGN.md 9b) ----
+ * Geometry needs nothing new: cris_preprocess_batch applies whatever inverse matrix the descriptor carries (rotation, mirror,
+ * scale and shift included).  The colour jitter is THIS PROJECT'S OWN definition - fixed order brightness, contrast, saturation,
+ * no hue - and is not pinned against another library.
+ * cris_gray_sum_batch: one launch for the ragged batch, sums[b] += sum over the source pixels of 77 R + 150 G + 29 B as an exact
+ * integer (64-bit accumulators throughout: a 32-bit one wraps after 65 793 white pixels; wave shuffle, LDS, one 64-bit atomic add
+ * per block - exact and order-free).  sums_dev [n] is zeroed by the caller; the kernel ADDS.  The images are read as whole
+ * dwords (4 pixels per 3 dwords), so every img must be non-NULL and 4-byte aligned: samples_host, the HOST copy of the same n
+ * descriptors, is what the launcher checks that on before the launch (the way cris_eval_iou_batch takes both copies); only
+ * samples_dev is read by the kernel.  H, W > 0. */
+int cris_gray_sum_batch(const cris_sample_desc* samples_host, const cris_sample_desc* samples_dev, int n, unsigned long long* sums_dev,
+                        void* stream);
+/* cris_preprocess_batch_aug: the arguments and the warp code of cris_preprocess_batch (one template, two instantiations) plus
+ * factors_dev [n][3] = (fb, fc, fs) per sample, sums_dev [n] from cris_gray_sum_batch (may be NULL when no sample has fc != 1),
+ * unit_dev [256] with unit[v] = float32(v) / float32(255) built on the host, norm = HOST array of 6 floats (mean rgb, std rgb).
+ * The 8-bit cubic result v_c of a pixel becomes, every step one separately rounded float32 operation (never fused):
+ *     x_c = clamp01(unit[v_c] * fb)
+ *     mean = (float)((double)sums[b] / (65280.0 * (double)H * (double)W)) ;  pivot = min(fb * mean, 1)
+ *     k = (1 - fc) * pivot ;  x_c = clamp01(x_c * fc + k)
+ *     g = 0.299f * x_r + 0.587f * x_g + 0.114f * x_b   (left to right)
+ *     x_c = clamp01(x_c * fs + (1 - fs) * g)
+ *     out_c = (x_c - mean_c) / std_c                    (IEEE division)
+ * A sample whose three factors are all exactly 1.0f, and any destination pixel none of whose 16 cubic taps lies inside the source
+ * (pure letter-box border), go through lut_img exactly as in cris_preprocess_batch.  The mask path is unchanged. */
+int cris_preprocess_batch_aug(const cris_sample_desc* samples_dev, int n, int S_h, int S_w, const short* tab_linear, const short* tab_cubic,
+                              const float* lut_img, const float* lut_mask, const unsigned char* border_rgb /* host, 3 bytes */,
+                              const float* factors_dev, const unsigned long long* sums_dev, const float* unit_dev,
+                              const float* norm /* host, 6 floats */, float* img_out, float* mask_out, void* stream);
 /* host: inv = cv::invertAffineTransform(mat) (2x3 doubles) */
 int cris_invert_affine(const double* mat, double* inv);
 /* host: the 16-bit remap weight tables of cv::initInterTab2D(fixpt): tab_linear [1024][4], tab_cubic [1024][16] (copy to the device) */
