@@ -181,6 +181,41 @@ struct ep_cubic_tab {
     float tab[32][4];
 };
 
+// The arithmetic both batch kernels share, written once.  ep_warp_row: the fixed-point source coordinates of destination row y
+// (cv::warpAffine's X0 / Y0); ep_warp_value: the value of destination pixel x of that row - warp_affine_cubic_kernel's, operation
+// for operation.  `tab` is the block's LDS copy of the 32 x 4 coefficient table.  Both live inside this file's no-contraction
+// region and are inlined: eval_iou_batch_kernel compiles to the instructions it had with the code written out in place (only the
+// operand order of some commutative multiplies differs: DESIGN.md 9b).
+__device__ __forceinline__ void ep_warp_row(const double* m, int y, long& X0, long& Y0) {
+    const double AB = (double)(1 << EP_AB_BITS);
+    const int round_delta = (1 << EP_AB_BITS) / (1 << EP_INTER_BITS) / 2;
+    X0 = (long)rint(ep_dmul(ep_dadd(ep_dmul(m[1], (double)y), m[2]), AB)) + round_delta;
+    Y0 = (long)rint(ep_dmul(ep_dadd(ep_dmul(m[4], (double)y), m[5]), AB)) + round_delta;
+}
+
+__device__ __forceinline__ float ep_warp_value(const float* __restrict__ src, int H, int W, const float (*tab)[4], const double* m, long X0,
+                                               long Y0, int x, float border) {
+    const double AB = (double)(1 << EP_AB_BITS);
+    const long adelta = (long)rint(ep_dmul(ep_dmul(m[0], (double)x), AB)), bdelta = (long)rint(ep_dmul(ep_dmul(m[3], (double)x), AB));
+    const long Xq = (X0 + adelta) >> (EP_AB_BITS - EP_INTER_BITS), Yq = (Y0 + bdelta) >> (EP_AB_BITS - EP_INTER_BITS);
+    const int sx = (int)(Xq >> EP_INTER_BITS) - 1, sy = (int)(Yq >> EP_INTER_BITS) - 1;
+    const int fx = (int)(Xq & 31), fy = (int)(Yq & 31);
+    float acc = 0.f;
+#pragma unroll
+    for (int ky = 0; ky < 4; ++ky) {
+        const int yy = sy + ky;
+#pragma unroll
+        for (int kx = 0; kx < 4; ++kx) {
+            const int xx = sx + kx;
+            const bool inside = yy >= 0 && yy < H && xx >= 0 && xx < W;
+            const float v = inside ? src[(size_t)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)] : border;
+            const float wgt = ep_mul(tab[fy][ky], tab[fx][kx]);
+            acc = ep_add(acc, ep_mul(v, wgt));
+        }
+    }
+    return acc;
+}
+
 __global__ __launch_bounds__(256) void eval_iou_batch_kernel(const float* __restrict__ probs, int H, int W,
                                                              const cris_eval_desc* __restrict__ descs,
                                                              const unsigned char* __restrict__ masks, const ep_cubic_tab t, float thr,
@@ -194,37 +229,19 @@ __global__ __launch_bounds__(256) void eval_iou_batch_kernel(const float* __rest
     const unsigned char* __restrict__ mrow = masks + d.mask_off;
     const int gpr = d.pitch >> 2;                                  // groups per row (the pitch is a multiple of 4)
     const long total = (long)gpr * d.h_out;
-    const double AB = (double)(1 << EP_AB_BITS);
-    const int round_delta = (1 << EP_AB_BITS) / (1 << EP_INTER_BITS) / 2;
     int inter = 0, uni = 0;
     for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long)gridDim.x * blockDim.x) {
         const int y = (int)(g / gpr), x0 = (int)(g % gpr) * 4;
         const size_t boff = (size_t)y * d.pitch + x0;
         const unsigned int mword = *reinterpret_cast<const unsigned int*>(mrow + boff);
-        const long X0 = (long)rint(ep_dmul(ep_dadd(ep_dmul(d.m[1], (double)y), d.m[2]), AB)) + round_delta;
-        const long Y0 = (long)rint(ep_dmul(ep_dadd(ep_dmul(d.m[4], (double)y), d.m[5]), AB)) + round_delta;
+        long X0, Y0;
+        ep_warp_row(d.m, y, X0, Y0);
         unsigned int oword = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int x = x0 + j;
             if (x < d.w_out) {                                     // (lanes past w_out: padding bytes, not counted)
-                const long adelta = (long)rint(ep_dmul(ep_dmul(d.m[0], (double)x), AB)), bdelta = (long)rint(ep_dmul(ep_dmul(d.m[3], (double)x), AB));
-                const long Xq = (X0 + adelta) >> (EP_AB_BITS - EP_INTER_BITS), Yq = (Y0 + bdelta) >> (EP_AB_BITS - EP_INTER_BITS);
-                const int sx = (int)(Xq >> EP_INTER_BITS) - 1, sy = (int)(Yq >> EP_INTER_BITS) - 1;
-                const int fx = (int)(Xq & 31), fy = (int)(Yq & 31);
-                float acc = 0.f;
-#pragma unroll
-                for (int ky = 0; ky < 4; ++ky) {
-                    const int yy = sy + ky;
-#pragma unroll
-                    for (int kx = 0; kx < 4; ++kx) {
-                        const int xx = sx + kx;
-                        const bool inside = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                        const float v = inside ? src[(size_t)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)] : border;
-                        const float wgt = ep_mul(tab[fy][ky], tab[fx][kx]);
-                        acc = ep_add(acc, ep_mul(v, wgt));
-                    }
-                }
+                const float acc = ep_warp_value(src, H, W, tab, d.m, X0, Y0, x, border);
                 const bool p = acc > thr, m = ((mword >> (8 * j)) & 0xffu) != 0u;
                 inter += (p && m) ? 1 : 0;
                 uni += (p || m) ? 1 : 0;
@@ -246,6 +263,76 @@ __global__ __launch_bounds__(256) void eval_iou_batch_kernel(const float* __rest
     if (threadIdx.x == 0) {
         atomicAdd(counts + 2 * (size_t)d.row, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
         atomicAdd(counts + 2 * (size_t)d.row + 1, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+    }
+}
+
+// ---- prediction without ground truth: warp + threshold + (area, score, bounding box) for n ragged descriptors in one launch ----
+// The grid, the 4-pixel groups, the per-pixel value and the mask bytes are eval_iou_batch_kernel's; no mask is read.  Over the
+// pixels with value > thr, row d.row of the table stats [rows][6] of unsigned 64-bit words receives
+//     [0] += 1    [1] += (long long)rintf(value * 65536.f)    [2] min= x    [3] min= y    [4] max= x + 1    [5] max= y + 1
+// (65536 is a power of two: the product is exact, rintf rounds half to even; value > thr >= 0, so every term is positive and the
+// unsigned atomics are the signed ones).  Integer add / min / max are exact and order-free: wave shuffle, the block's 4 waves
+// through LDS, then one set of six 64-bit atomics per block that found a pixel - every run gives the same table.
+__global__ __launch_bounds__(256) void predict_masks_batch_kernel(const float* __restrict__ probs, int H, int W,
+                                                                  const cris_eval_desc* __restrict__ descs, const ep_cubic_tab t, float thr,
+                                                                  float border, unsigned long long* __restrict__ stats,
+                                                                  unsigned char* __restrict__ out) {
+    __shared__ float tab[32][4];
+    __shared__ unsigned long long red_score[4];
+    __shared__ int red[5][4];
+    if (threadIdx.x < 128) tab[threadIdx.x >> 2][threadIdx.x & 3] = t.tab[threadIdx.x >> 2][threadIdx.x & 3];
+    __syncthreads();
+    const cris_eval_desc d = descs[blockIdx.y];
+    const float* __restrict__ src = probs + (size_t)d.map * H * W;
+    const int gpr = d.pitch >> 2;                                  // groups per row (the pitch is a multiple of 4)
+    const long total = (long)gpr * d.h_out;
+    int area = 0, x_min = 0x7fffffff, y_min = 0x7fffffff, x_end = 0, y_end = 0;     // (w_out * h_out < 2^31: a launch's area fits)
+    unsigned long long score = 0;
+    for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long)gridDim.x * blockDim.x) {
+        const int y = (int)(g / gpr), x0 = (int)(g % gpr) * 4;
+        long X0, Y0;
+        ep_warp_row(d.m, y, X0, Y0);
+        unsigned int oword = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = x0 + j;
+            if (x < d.w_out) {                                     // (lanes past w_out: padding bytes, not counted)
+                const float acc = ep_warp_value(src, H, W, tab, d.m, X0, Y0, x, border);
+                if (acc > thr) {
+                    area += 1;
+                    score += (unsigned long long)(long long)rintf(ep_mul(acc, 65536.f));
+                    x_min = min(x_min, x); x_end = max(x_end, x + 1);
+                    y_min = min(y_min, y); y_end = max(y_end, y + 1);
+                    oword |= 0xffu << (8 * j);
+                }
+            }
+        }
+        if (out) *reinterpret_cast<unsigned int*>(out + d.out_off + (size_t)y * d.pitch + x0) = oword;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        area += __shfl_xor(area, o, 64);
+        score += __shfl_xor(score, o, 64);
+        x_min = min(x_min, __shfl_xor(x_min, o, 64)); y_min = min(y_min, __shfl_xor(y_min, o, 64));
+        x_end = max(x_end, __shfl_xor(x_end, o, 64)); y_end = max(y_end, __shfl_xor(y_end, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        const int w = threadIdx.x >> 6;
+        red_score[w] = score;
+        red[0][w] = area; red[1][w] = x_min; red[2][w] = y_min; red[3][w] = x_end; red[4][w] = y_end;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int a = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        if (a > 0) {                                               // (a block without a pixel would add 0 and min / max nothing)
+            unsigned long long* row = stats + 6 * (size_t)d.row;
+            atomicAdd(row, (unsigned long long)a);
+            atomicAdd(row + 1, red_score[0] + red_score[1] + red_score[2] + red_score[3]);
+            atomicMin(row + 2, (unsigned long long)min(min(red[1][0], red[1][1]), min(red[1][2], red[1][3])));
+            atomicMin(row + 3, (unsigned long long)min(min(red[2][0], red[2][1]), min(red[2][2], red[2][3])));
+            atomicMax(row + 4, (unsigned long long)max(max(red[3][0], red[3][1]), max(red[3][2], red[3][3])));
+            atomicMax(row + 5, (unsigned long long)max(max(red[4][0], red[4][1]), max(red[4][2], red[4][3])));
+        }
     }
 }
 
@@ -282,6 +369,37 @@ extern "C" int cris_eval_iou_batch(const float* probs, int P, int H, int W, cons
     const int cap = 2048 / n > 8 ? 2048 / n : 8;                   // ~2048 blocks in all, grid-stride for the rest
     hipLaunchKernelGGL(eval_iou_batch_kernel, dim3(cris_grid_1d(most, 256, cap), n), dim3(256), 0, (hipStream_t)stream, probs, H, W,
                        descs_dev, masks, t, thr, border, counts, out_masks);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cris_predict_masks_batch(const float* probs, int P, int H, int W, const cris_eval_desc* descs_host,
+                                        const cris_eval_desc* descs_dev, int n, float thr, float border, long long* stats, int stat_rows,
+                                        unsigned char* out_masks, size_t out_bytes, void* stream) {
+    CRIS_CHECK_ARG(probs && descs_host && descs_dev && stats, "null operand");
+    CRIS_CHECK_ARG(P > 0 && H > 0 && W > 0 && stat_rows > 0, "bad sizes");
+    CRIS_CHECK_ARG(n > 0 && n <= 65535, "n must be in 1 .. 65535");
+    CRIS_CHECK_ARG(thr >= 0.f && thr <= 3.0e38f, "thr must be finite and >= 0 (counted values are positive)");      // (false for a NaN)
+    CRIS_CHECK_ARG(border >= -3.0e38f && border <= 3.0e38f, "border must be finite");
+    CRIS_CHECK_ARG(((uintptr_t)stats & 7) == 0 && ((uintptr_t)out_masks & 3) == 0, "stats must be 8-byte, out_masks 4-byte aligned");
+    long most = 0;
+    for (int i = 0; i < n; ++i) {                                  // every address the kernel forms is checked here, on the host copy
+        const cris_eval_desc& d = descs_host[i];
+        CRIS_CHECK_ARG(d.w_out > 0 && d.h_out > 0 && (long)d.w_out * d.h_out < (1L << 31), "descriptor: bad output size");
+        CRIS_CHECK_ARG(d.map >= 0 && d.map < P, "descriptor: map out of range");
+        CRIS_CHECK_ARG(d.row >= 0 && d.row < stat_rows, "descriptor: row out of range");
+        CRIS_CHECK_ARG(d.pitch >= d.w_out && (d.pitch & 3) == 0 && d.pitch - d.w_out < (1 << 20), "descriptor: the pitch must be a multiple of 4, >= w_out");
+        if (out_masks)
+            CRIS_CHECK_ARG(d.out_off >= 0 && (d.out_off & 3) == 0 && (size_t)d.out_off + (size_t)d.pitch * d.h_out <= out_bytes,
+                           "descriptor: output outside the buffer");
+        const long groups = (long)(d.pitch >> 2) * d.h_out;
+        if (groups > most) most = groups;
+    }
+    ep_cubic_tab t;
+    ep_warp_setup(nullptr, nullptr, t.tab);
+    const int cap = 2048 / n > 8 ? 2048 / n : 8;                   // the grid of cris_eval_iou_batch
+    hipLaunchKernelGGL(predict_masks_batch_kernel, dim3(cris_grid_1d(most, 256, cap), n), dim3(256), 0, (hipStream_t)stream, probs, H, W,
+                       descs_dev, t, thr, border, reinterpret_cast<unsigned long long*>(stats), out_masks);
     CRIS_LAUNCH_CHECK();
     return 0;
 }

@@ -11,7 +11,9 @@ libcris_hip.so (csrc/evalpost.hip) and only the two integer counts per sample co
 
 `validate_batch` is the per-sample form (one warp and one count launch per sample, float masks).  `iou_batch` is the batched
 form that evaluate.Evaluator drives: steps 3-4 for a whole ragged batch in ONE launch, uint8 masks and the descriptor table
-packed into one pinned buffer (`EvalStaging`), the warped map never written, counts accumulated in a table for the whole pass."""
+packed into one pinned buffer (`EvalStaging`), the warped map never written, counts accumulated in a table for the whole pass.
+`predict_batch` is the same launch without ground truth (predict.Predictor): no mask goes up (`EvalStaging.pack_sizes`), the
+binary masks come out at the original sizes and (area, score, bounding box) accumulate in an int64 table (`new_predict_stats`)."""
 import ctypes as C
 
 import numpy as np
@@ -132,6 +134,24 @@ class EvalStaging:
         self.n, self.out_bytes = len(descs), out_off
         return self
 
+    def pack_sizes(self, shapes, descs):
+        """`pack` without ground truth (predict_batch): shapes: (h, w) per image; descs: (mat, shape index, map index, stats row)
+        per descriptor.  Only the descriptor table is filled and uploaded - no mask bytes (mask_bytes = 0, every mask_off 0 and
+        ignored); pitch, out_off and out_bytes are computed as `pack` computes them."""
+        shapes = [(int(h), int(w)) for h, w in shapes]
+        if len(descs) > self.max_descs:
+            self._reserve(len(descs), self.mask_cap)
+        self.wait()
+        out_off = 0
+        for i, (mat, si, mp, row) in enumerate(descs):
+            m = np.ascontiguousarray(np.asarray(mat, dtype=np.float64).reshape(6))
+            h, w = shapes[si]
+            pitch = self._up(w, 4)
+            hip.call("cris_eval_desc_fill", C.addressof(self.descs[i]), m.ctypes.data_as(C.c_void_p), w, h, int(mp), 0, pitch, out_off, int(row))
+            out_off += self._up(pitch * h, self.ALIGN)
+        self.n, self.mask_bytes, self.out_bytes = len(descs), 0, out_off
+        return self
+
     def upload(self):
         """one asynchronous copy of the descriptor table and the masks (the used prefix of the buffer) on the current stream"""
         end = self.mask_base + self.mask_bytes
@@ -166,3 +186,36 @@ def iou_batch(probs, descs, masks_u8, counts, row0, thr=0.35, out_masks=None, bo
     hip.call("cris_eval_iou_batch", ptr(probs), P, H, W, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n, ptr(masks_u8),
              masks_u8.numel(), float(thr), float(border), counts.data_ptr() + 8 * int(row0), counts.shape[0] - int(row0),
              ptr(out_masks), 0 if out_masks is None else out_masks.numel(), _stream())
+
+
+PREDICT_FIELDS = ("area", "score_q16", "x_min", "y_min", "x_end", "y_end")
+PREDICT_INIT = (0, 0, 2 ** 31 - 1, 2 ** 31 - 1, 0, 0)
+
+
+def new_predict_stats(rows, device):
+    """the initialised statistics table of `predict_batch`: int64 [rows, 6], every row (0, 0, 2^31 - 1, 2^31 - 1, 0, 0) - the
+    neutral elements of the kernel's add, add, min, min, max, max (PREDICT_FIELDS)"""
+    if int(rows) <= 0:
+        raise ValueError("new_predict_stats: rows must be positive")
+    return torch.tensor(PREDICT_INIT, dtype=torch.int64).repeat(int(rows), 1).to(device)
+
+
+def predict_batch(probs, descs, stats, row0, thr=0.35, out_masks=None, border=0.0):
+    """ONE launch for a whole batch WITHOUT ground truth (cris_predict_masks_batch): for every descriptor of `descs` (an
+    uploaded EvalStaging, `pack_sizes` or `pack`) the inverse warp of probs[map] to the original size - iou_batch's values, bit
+    for bit - the threshold, and over the pixels above it stats[row0 + row] (+=, +=, min, min, max, max)= (1, rint(value * 65536),
+    x, y, x + 1, y + 1).  probs: [P, H, W] cuda fp32 (sigmoid_upsample); stats: [R, 6] cuda int64 from new_predict_stats;
+    out_masks: optional device uint8 buffer of descs.out_bytes that receives (warp > thr) * 255 per descriptor (pitch
+    descs.descs[i].pitch, descriptor i at descs.descs[i].out_off); None = statistics only."""
+    if probs.device.type != "cuda":
+        raise RuntimeError("evalpost runs on the GPU only (no CPU fallback)")
+    if probs.dim() != 3 or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise ValueError("predict_batch: probs must be contiguous fp32 [P, H, W]")
+    if stats.dtype != torch.int64 or stats.dim() != 2 or stats.shape[1] != 6 or not stats.is_contiguous() or not 0 <= row0 < stats.shape[0]:
+        raise ValueError("predict_batch: stats must be contiguous int64 [R, 6] and row0 inside it")
+    if out_masks is not None and (out_masks.dtype != torch.uint8 or not out_masks.is_contiguous() or out_masks.numel() < descs.out_bytes):
+        raise ValueError("predict_batch: out_masks must be a contiguous uint8 buffer of at least descs.out_bytes")
+    P, H, W = probs.shape
+    hip.call("cris_predict_masks_batch", ptr(probs), P, H, W, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n, float(thr),
+             float(border), stats.data_ptr() + 48 * int(row0), stats.shape[0] - int(row0), ptr(out_masks),
+             0 if out_masks is None else out_masks.numel(), _stream())

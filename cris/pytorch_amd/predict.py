@@ -1,0 +1,256 @@
+"""Referring segmentation of UNLABELED images: masks at the original size plus area, bounding box and confidence per expression.
+
+    pred = Predictor(model, RecordPipeline(size, word_len, device, mode="test"), thr=0.35)
+    out = pred.predict(images, expressions, images_per_batch=8, masks="host")
+    out[i][j] -> Prediction(sentence, mask, area, box, score)
+
+The reference has no such entry point: its `engine.inference` (engine/engine.py:146-215) needs a ground-truth mask per record and
+does the last steps per expression on the host (cv2.warpAffine, threshold, numpy).  Here a batch is JPEG decode + letter-box on the
+GPU (jpegdec, inputpipe), one visual pass per image (`segment` / `segment_expressions`), `evalpost.sigmoid_upsample` and ONE launch
+of `evalpost.predict_batch` (csrc/evalpost.hip cris_predict_masks_batch): inverse warp of every expression to its image's size,
+threshold, mask bytes, and integer (area, score, box) statistics in a device table.  Nothing but JPEG bytes and descriptors goes
+up; the table of the whole call comes back once at the end, the masks once per batch.  Batching and padding follow
+`evaluate.Evaluator.inference` (a short last image batch repeats its last image, the expression count is padded to a multiple of
+8 by repeating the last expression), so one graph is captured per shape.
+
+    python -m cris.pytorch_amd.predict --weights CKPT --config YAML --image F --expr "the left one" --out-prefix P
+"""
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import evalpost
+
+Prediction = namedtuple("Prediction", "sentence mask area box score")
+Prediction.__doc__ = """sentence: the expression; mask: uint8 [h, w] of 0 / 255 at the image's own size (numpy array, CUDA tensor view or
+None: `masks`); area: pixels above the threshold; box: (x0, y0, x1, y1) half-open, None when area == 0; score: the mean warped
+probability over those pixels, score_q16 / (65536 * area) in float64 (each pixel's value rounded to 1 / 65536), 0.0 when area == 0"""
+
+BatchPlan = namedtuple("BatchPlan", "lo n image_index index descs")
+BatchPlan.__doc__ = """images lo .. lo + n of the call; image_index: the batch's images padded to images_per_batch by repeating the last
+one; index: image (within the batch) of every expression, padded to a multiple of `multiple` by repeating the last one; descs:
+(inverse or None, image within the batch, probability map, statistics row of the WHOLE call) per real expression"""
+
+MASK_MODES = ("host", "device", None)
+
+
+def _pad_to(n, multiple):
+    return (n + multiple - 1) // multiple * multiple
+
+
+def plan_predict(sents_per_image, images_per_batch=8, multiple=8, inverses=None):
+    """Host arithmetic of a whole predict call: image i has sents_per_image[i] >= 1 expressions; the images are cut into batches
+    of `images_per_batch` and each batch is planned as evaluate.plan_inference plans it.  Statistics rows run 0, 1, 2 ... over
+    the expressions of the call in order; the padding (images and expressions) gets no descriptor.  `inverses`: optional 2x3
+    matrices per image (param['inverse']) placed into the descriptors; None leaves the slot None (the matrices of a batch are
+    known once its images are decoded).  Returns the list of BatchPlan."""
+    counts = [int(k) for k in sents_per_image]
+    if not counts or min(counts) < 1:
+        raise ValueError("plan_predict: every image needs at least one expression")
+    if images_per_batch < 1 or multiple < 1:
+        raise ValueError("plan_predict: images_per_batch and multiple must be positive")
+    if inverses is not None and len(inverses) != len(counts):
+        raise ValueError("plan_predict: %d inverses for %d images" % (len(inverses), len(counts)))
+    plans, row = [], 0
+    for lo in range(0, len(counts), images_per_batch):
+        part = counts[lo:lo + images_per_batch]
+        n = len(part)
+        index = [i for i, k in enumerate(part) for _ in range(k)]
+        descs = [(None if inverses is None else inverses[lo + i], i, k, row + k) for k, i in enumerate(index)]
+        row += len(index)
+        plans.append(BatchPlan(lo, n, list(range(n)) + [n - 1] * (images_per_batch - n),
+                               index + [index[-1]] * (_pad_to(len(index), multiple) - len(index)), descs))
+    return plans
+
+
+def _check_inputs(images, expressions, images_per_batch, masks):
+    """-> (kind 'bytes' / 'array', expressions as lists); everything here is host-only"""
+    if masks not in MASK_MODES:
+        raise ValueError("predict: masks must be 'host', 'device' or None, got %r" % (masks,))
+    if int(images_per_batch) < 1:
+        raise ValueError("predict: images_per_batch must be positive")
+    images, expressions = list(images), list(expressions)
+    if not images:
+        raise ValueError("predict: no images")
+    if len(images) != len(expressions):
+        raise ValueError("predict: %d images but %d expression entries" % (len(images), len(expressions)))
+    exprs = []
+    for i, e in enumerate(expressions):
+        e = [e] if isinstance(e, str) else list(e) if isinstance(e, (list, tuple)) else None
+        if not e or not all(isinstance(s, str) and s.strip() for s in e):
+            raise ValueError("predict: expressions[%d] must be a non-empty str or a non-empty list of non-empty str" % i)
+        exprs.append(e)
+    is_bytes = [isinstance(im, (bytes, bytearray, memoryview)) for im in images]
+    if all(is_bytes):
+        return "bytes", images, exprs
+    if any(is_bytes):
+        raise ValueError("predict: images must be all JPEG bytes or all decoded arrays (one kind per call)")
+    for i, im in enumerate(images):
+        shape, dtype = getattr(im, "shape", None), getattr(im, "dtype", None)
+        if shape is None or len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1 or str(dtype) not in ("uint8", "torch.uint8"):
+            raise ValueError("predict: images[%d] must be JPEG bytes or a uint8 RGB array / tensor [h, w, 3]" % i)
+    return "array", images, exprs
+
+
+class Predictor:
+    """`Predictor(model, pipeline, thr=0.35)`: model - an InferenceRunner, the drop-in CRIS module in eval mode, or any callable
+    `(img, word) -> logits [B, 1, h, w]`; when it offers `segment(img, word, image_index)` or `segment_expressions`, the visual
+    encoder runs once per image, otherwise `model(img[index], word)` is called.  pipeline - a RecordPipeline in mode "test" (its
+    preprocessor, tokenizer, word length and decode threads are used; no record is needed)."""
+
+    RING = 3            # descriptor staging buffers in flight (evaluate.Evaluator.RING)
+
+    def __init__(self, model, pipeline, thr=0.35):
+        if getattr(pipeline, "mode", None) != "test":
+            raise ValueError("Predictor needs a RecordPipeline in mode 'test', got %r" % (getattr(pipeline, "mode", None),))
+        thr = float(thr)
+        if not 0.0 <= thr < float("inf"):
+            raise ValueError("Predictor: thr must be finite and >= 0, got %r" % (thr,))
+        self.model, self.pipe, self.thr = model, pipeline, thr
+        self.device = pipeline.device
+        self._segment = getattr(model, "segment", None) or getattr(model, "segment_expressions", None)
+        self._ring, self._turn = None, 0
+
+    def _staging(self):
+        if self._ring is None:          # (the first device allocation: after every argument check)
+            self._ring = [evalpost.EvalStaging(self.device, mask_bytes=16) for _ in range(self.RING)]
+        self._turn = (self._turn + 1) % self.RING
+        return self._ring[self._turn]
+
+    @torch.no_grad()
+    def predict(self, images, expressions, images_per_batch=8, masks="host"):
+        """images: JPEG bytes per image, or uint8 RGB [h, w, 3] arrays / tensors per image (one kind per call; JPEG files come
+        back turned by their EXIF orientation, as cv2.imdecode returns them).  expressions: per image a str or a non-empty list
+        of str.  masks: "host" (numpy arrays, one device-to-host copy per batch), "device" (views of one CUDA buffer per batch)
+        or None (statistics only: no mask buffer is allocated).  Returns a list per image of Prediction per expression."""
+        from . import jpegdec
+        kind, images, exprs = _check_inputs(images, expressions, images_per_batch, masks)
+        images_per_batch = int(images_per_batch)
+        plans = plan_predict([len(e) for e in exprs], images_per_batch)
+        total = sum(len(e) for e in exprs)
+        table = evalpost.new_predict_stats(total, self.device)
+        kept = []                                                      # per expression: its mask (or None)
+        for b in plans:
+            part = images[b.lo:b.lo + b.n]
+            if kind == "bytes":
+                part = jpegdec.decode_batch([bytes(f) for f in part], self.device, threads=self.pipe.threads)
+            img, _, _, invs = self.pipe.pre(part, None)
+            shapes = [(int(t.shape[0]), int(t.shape[1])) for t in part]
+            if b.n < images_per_batch:                                 # short last batch: repeat its last image, one graph shape
+                img = img[torch.tensor(b.image_index, device=self.device)]
+            sents = [s for e in exprs[b.lo:b.lo + b.n] for s in e]
+            K = len(sents)
+            word = self.pipe.tok.tokenize(sents + [sents[-1]] * (len(b.index) - K), self.pipe.word_length, True)
+            word = word.to(self.device, non_blocking=True)
+            st = self._staging().pack_sizes(shapes, [(invs[i], i, k, row) for _, i, k, row in b.descs]).upload()
+            if self._segment is not None:
+                logits = self._segment(img, word, b.index)
+            else:
+                logits = self.model(img[torch.tensor(b.index, device=self.device)], word)
+            probs = evalpost.sigmoid_upsample(logits, img.shape[-2], img.shape[-1])
+            out = None if masks is None else torch.empty(st.out_bytes, dtype=torch.uint8, device=self.device)
+            evalpost.predict_batch(probs, st, table, 0, self.thr, out_masks=out)
+            if masks is None:
+                kept += [None] * K
+                continue
+            buf = out.cpu().numpy() if masks == "host" else out        # the batch's masks: one copy
+            for k in range(K):
+                d = st.descs[k]
+                m = buf[d.out_off:d.out_off + d.pitch * d.h_out].reshape(d.h_out, d.pitch)[:, :d.w_out]
+                kept.append(np.ascontiguousarray(m) if masks == "host" else m)
+        stats = table.cpu().numpy()                                    # the call's one read of the statistics
+        result, k = [], 0
+        for e in exprs:
+            row = []
+            for s in e:
+                area, q16, x0, y0, x1, y1 = (int(v) for v in stats[k])
+                row.append(Prediction(s, kept[k], area, (x0, y0, x1, y1) if area else None, q16 / (65536.0 * area) if area else 0.0))
+                k += 1
+            result.append(row)
+        return result
+
+
+class _WordHashTokenizer:
+    """--synthetic only, where the CLIP merge list is not installed: the tokenizer's interface with deterministic word-hash ids
+    (random weights attach no meaning to an id anyway)"""
+
+    def tokenize(self, texts, context_length=77, truncate=False):
+        texts = [texts] if isinstance(texts, str) else texts
+        out = torch.zeros(len(texts), context_length, dtype=torch.long)
+        for i, t in enumerate(texts):
+            ids = [49406] + [1 + (sum(map(ord, w)) % 40000) for w in t.lower().split()][:context_length - 2] + [49407]
+            out[i, :len(ids)] = torch.tensor(ids)
+        return out
+
+
+def _load_config(path):
+    """the reference's yaml layout (config/refcoco/cris_r50.yaml: sections of key: value) flattened to one dict"""
+    import yaml
+    with open(path) as f:
+        doc = yaml.safe_load(f)
+    flat = {}
+    for k, v in doc.items():
+        if isinstance(v, dict):
+            flat.update(v)
+        else:
+            flat[k] = v
+    return flat
+
+
+def main(argv=None):
+    import argparse
+    import os
+
+    from PIL import Image
+
+    from . import arch, records, tokenizer
+    from .infer import InferenceRunner
+    from .model.segmenter import head_spec_from_cfg
+    ap = argparse.ArgumentParser(description="segment referring expressions in one image; writes PREFIX_<j>.png per expression")
+    ap.add_argument("--weights", help="checkpoint with a reference-keyed 'state_dict' (not needed with --synthetic)")
+    ap.add_argument("--config", help="the yaml the model was trained with (not needed with --synthetic)")
+    ap.add_argument("--image", required=True, help="a JPEG file, or any image file Pillow opens")
+    ap.add_argument("--expr", action="append", required=True, help="a referring expression; repeat for several")
+    ap.add_argument("--out-prefix", required=True)
+    ap.add_argument("--thr", type=float, default=0.35)
+    ap.add_argument("--synthetic", nargs="?", const="r50", default=None, metavar="SPEC",
+                    help="arch.synthetic_state_dict of r50 (default), r101 or tiny instead of --weights / --config")
+    ap.add_argument("--size", type=int, default=None, help="network input size (default: the config's input_size, 416)")
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("predict needs a GPU (there is no CPU fallback)")
+    dev = torch.device("cuda:0")
+    if a.synthetic:
+        clip, head = arch.specs_by_name(a.synthetic)
+        sd, size = arch.synthetic_state_dict(clip, head, 0), a.size or (96 if a.synthetic == "tiny" else 416)
+    else:
+        if not a.weights or not a.config:
+            raise SystemExit("--weights and --config are required without --synthetic")
+        cfg = _load_config(a.config)
+        ck = torch.load(a.weights, map_location="cpu")
+        sd = ck.get("state_dict", ck)
+        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+        clip = arch.clip_spec_from_state_dict({k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")})
+        head, size = head_spec_from_cfg(cfg), a.size or int(cfg.get("input_size", 416))
+    tok = tokenizer.BPETokenizer() if tokenizer.default_merges_path() else None
+    if tok is None:
+        if not a.synthetic:
+            raise SystemExit("the CLIP merge list (bpe_simple_vocab_16e6.txt.gz) was not found: see tokenizer.default_merges_path")
+        tok = _WordHashTokenizer()
+    pipe = records.RecordPipeline(size, head.word_len, dev, mode="test", tokenizer=tok)
+    runner = InferenceRunner(clip, head, sd, dev, use_graph=False)
+    with open(a.image, "rb") as f:
+        data = f.read()
+    image = data if data[:2] == b"\xff\xd8" else np.array(Image.open(a.image).convert("RGB"))
+    out = Predictor(runner, pipe, thr=a.thr).predict([image], [a.expr], images_per_batch=1, masks="host")[0]
+    os.makedirs(os.path.dirname(os.path.abspath(a.out_prefix)), exist_ok=True)
+    for j, p in enumerate(out):
+        path = "%s_%d.png" % (a.out_prefix, j)
+        Image.fromarray(p.mask, "L").save(path)
+        print("%s\t%r\tbox %s\tarea %d\tscore %.4f" % (path, p.sentence, p.box, p.area, p.score))
+    return out
+
+
+if __name__ == "__main__":
+    main()

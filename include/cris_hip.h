@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it) */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it) */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -523,6 +523,20 @@ int cris_eval_desc_fill(cris_eval_desc* desc, const double* mat, int w_out, int 
 int cris_eval_iou_batch(const float* probs, int P, int H, int W, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev,
                         int n, const unsigned char* masks, size_t mask_bytes, float thr, float border, int* counts, int count_rows,
                         unsigned char* out_masks, size_t out_bytes, void* stream);
+/* The same launch without ground truth (prediction on unlabeled images): n ragged descriptors, the grid, the per-pixel value (bit for
+ * bit cris_warp_affine_cubic's) and the mask bytes of cris_eval_iou_batch; mask_off is ignored and no mask is read.  out_masks (may be
+ * NULL: statistics only): (value > thr) * 255 as uint8 at out_off, row pitch `pitch`, padding bytes zero.  stats: int64 table
+ * [stat_rows][6], descriptor d updates row d.row = (area, score_q16, x_min, y_min, x_end, y_end): over the pixels with value > thr,
+ * area += 1, score_q16 += (long long)rintf(value * 65536.f) (a power-of-two scale: exact; half to even), x_min / y_min = min of x / y,
+ * x_end / y_end = max of x + 1 / y + 1.  The caller initialises a row to (0, 0, 2^31 - 1, 2^31 - 1, 0, 0); the kernel accumulates, so
+ * a second launch on the same row doubles the two sums and leaves the box.  Integer atomics (64-bit add / min / max, one set per
+ * block after a wave-shuffle + LDS reduction): exact, order-free, the same table on every run; mean score = score_q16 / (65536 area).
+ * Checked on the host before the launch: operands non-NULL (out_masks excepted), 0 <= thr finite, n in 1 .. 65535, row < stat_rows,
+ * map < P, pitch a multiple of 4 and >= w_out, w_out * h_out < 2^31, and with out_masks every out_off 4-byte aligned and inside
+ * out_bytes. */
+int cris_predict_masks_batch(const float* probs, int P, int H, int W, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev,
+                             int n, float thr, float border, long long* stats, int stat_rows, unsigned char* out_masks, size_t out_bytes,
+                             void* stream);
 /* ---- input preprocessing (reference utils/dataset.py:146-168 RefDataset.__getitem__, :207-221 convert; csrc/inputpipe.hip) ----
  * One launch per batch: img_out[b] = ((cv2.warpAffine(rgb_u8, mat, (S_w, S_h), INTER_CUBIC, borderValue=border_rgb).float()
  * / 255 - mean) / std) as [3][S_h][S_w] (through lut_img [3][256]), mask_out[b] = cv2.warpAffine(mask_u8, mat, ...,
