@@ -107,7 +107,7 @@ __device__ __forceinline__ void gemm_epilogue_fast32(const cris_conv_gemm_params
                 s1 += x;
                 const bf16_t xb = f2bf_hw(x);
                 __builtin_amdgcn_raw_buffer_store_b16((short)xb, rsO, vo[e & 3], so, CRIS_STORE_AUX);
-                if (bnr) {                          // as bn_bwd_reduce_fast_kernel (MASK 2) on the STORED gradient
+                if (bnr) {                          // as bn_bwd_reduce_kernel (MASK 2) on the STORED gradient
                     const float g = (yv[e] * b_sc + b_sh) > 0.f ? bf2f(xb) : 0.f;
                     b0 += g;
                     b1 += g * ((yv[e] - b_mean) * b_inv);

@@ -617,21 +617,38 @@ extern "C" int cris_bn_apply(const cris_bn_apply_params* pp, void* stream) {
 // ------------------------------------------------------------------------------------------------
 // BN backward: reduce (sum g, sum g*xhat [, branch 2]) then apply
 // ------------------------------------------------------------------------------------------------
-// gradient entering the BN output at full-resolution row m, channels c0..c0+7; also xhat (and xhat2)
+// Where the ReLU mask of a backward launch comes from - THE rule, for the reduce and apply launchers and the generic apply kernel:
+//   0: no ReLU; 1: from the stored forward output z (z > 0); 2: recomputed from scale*y + shift (pooled launches store no
+//   full-resolution z; two branches cannot be recomputed from one: the launchers refuse ReLU over y2 without z)
+__host__ __device__ __forceinline__ int bn_bwd_mask_mode(const cris_bn_bwd_params& p) {
+    return !p.relu ? 0 : (!p.pool && (p.y2 || p.z)) ? 1 : 2;
+}
+// The row math of the backward, stated once for channel j of a row's unpacked 8-channel vectors.  pos: the ReLU decision as
+// `mask` says (z is read for mask 1 only, sc / sh for mask 2 only).  g: the gradient entering the BN output - dz (already times
+// the forward multiplier, if any) times w (the pooling weight; 0 for a row that does not count) where pos.  xhat: the normalised input.
+__device__ __forceinline__ bool bn_bwd_pos(int mask, int j, const float* y, const float* z, const float* sc, const float* sh) {
+    if (mask == 1) return z[j] > 0.f;
+    if (mask == 2) return (y[j] * sc[j] + sh[j]) > 0.f;
+    return true;
+}
+__device__ __forceinline__ float bn_bwd_g(bool pos, float dz, float w) { return pos ? dz * w : 0.f; }
+__device__ __forceinline__ float bn_xhat(int j, const float* y, const float* mean, const float* inv) { return (y[j] - mean[j]) * inv[j]; }
+
+// g, xhat (and xhat2) at full-resolution row m, channels c0..c0+7, for the generic apply kernel: everything from memory, per row
 __device__ __forceinline__ void bn_bwd_point(const cris_bn_bwd_params& p, int m, int c0, float* g, float* xh, float* xh2) {
     float y[8], mean[8], inv[8];
     load8bf(p.y + (size_t)m * p.ldy + p.y_coff + c0, y);
     load8f(p.mean + c0, mean);
     load8f(p.invstd + c0, inv);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) xh[j] = (y[j] - mean[j]) * inv[j];
+    for (int j = 0; j < 8; ++j) xh[j] = bn_xhat(j, y, mean, inv);
     if (p.y2) {
         float y2[8], m2[8], i2[8];
         load8bf(p.y2 + (size_t)m * p.ldy2 + p.y2_coff + c0, y2);
         load8f(p.mean2 + c0, m2);
         load8f(p.invstd2 + c0, i2);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) xh2[j] = (y2[j] - m2[j]) * i2[j];
+        for (int j = 0; j < 8; ++j) xh2[j] = bn_xhat(j, y2, m2, i2);
     }
     const int HW = p.H * p.W;
     int mo = m;
@@ -644,25 +661,18 @@ __device__ __forceinline__ void bn_bwd_point(const cris_bn_bwd_params& p, int m,
         mo = (b * (p.H / 2) + (h >> 1)) * (p.W / 2) + (w >> 1);
         gscale = 0.25f;
     }
-    float dz[8];
+    float dz[8], z[8], sc[8], sh[8];
     load8bf(p.dz + (size_t)mo * p.lddz + p.dz_coff + c0, dz);
-    // ReLU mask
-    bool pos[8];
-    if (!p.relu) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pos[j] = true;
-    } else if (!p.pool && (p.y2 || p.z)) {
-        float z[8];
+    const int mask = bn_bwd_mask_mode(p);
+    if (mask == 1) {
         load8bf(p.z + (size_t)m * p.ldz + p.z_coff + c0, z);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pos[j] = z[j] > 0.f;
-    } else {
-        float sc[8], sh[8];
+    } else if (mask == 2) {
         load8f(p.scale + c0, sc);
         load8f(p.shift + c0, sh);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pos[j] = (y[j] * sc[j] + sh[j]) > 0.f;
     }
+    bool pos[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pos[j] = bn_bwd_pos(mask, j, y, z, sc, sh);
     if (p.mul) {
         const int b = cris_div24(m, HW, small);
         float mu[8];
@@ -671,84 +681,22 @@ __device__ __forceinline__ void bn_bwd_point(const cris_bn_bwd_params& p, int m,
         for (int j = 0; j < 8; ++j) dz[j] *= mu[j];
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) g[j] = pos[j] ? dz[j] * gscale : 0.f;
+    for (int j = 0; j < 8; ++j) g[j] = bn_bwd_g(pos[j], dz[j], gscale);
 }
 
-// Geometry shared by the reduce and apply kernels: a block owns ONE chunk of `chv` 8-channel vectors (up to 64 channels) and a
-// range of rows; its 256 threads are chv vector lanes x 256/chv row lanes.  The reduce grid is chunks x row blocks with at most
-// 64 row blocks, so a channel's partial sums form a column of <= 64 entries that one small launch adds up in order
-// (deterministic, no atomics).
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const cris_bn_bwd_params p, int rows_per_block, int chv, int chunks) {
-    // Each thread owns one 8-channel vector and a strided subset of the block's rows (register accumulation); the RS row
-    // lanes of a vector are then combined through a plain LDS table + a column sum in lane order.
-    __shared__ float spart[3][256 * 8];            // [sum][thread-major: rsub * cvn*8 + cv_local*8 + j]
-    const int CV = p.C >> 3;
-    const int M = p.Bn * p.H * p.W;
-    const int chunk = blockIdx.x % chunks, rb = blockIdx.x / chunks;
-    const int r0 = rb * rows_per_block;
-    const int r1 = min(M, r0 + rows_per_block);
-    {
-        const int cvb = chunk * chv;
-        const int cvn = min(chv, CV - cvb);
-        const int RS = 256 / cvn;
-        const int cvl = (int)threadIdx.x % cvn;
-        const int cv = cvb + cvl;
-        const int rsub = threadIdx.x / cvn;
-        float a0[8], a1[8], a3[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a0[j] = a1[j] = a3[j] = 0.f;
-        if (rsub < RS) {
-            for (int m = r0 + rsub; m < r1; m += RS) {
-                float g[8], xh[8], xh2[8];
-                bn_bwd_point(p, m, cv * 8, g, xh, xh2);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    a0[j] += g[j];
-                    a1[j] += g[j] * xh[j];
-                    if (p.y2) a3[j] += g[j] * xh2[j];
-                }
-            }
-        }
-        if (rsub < RS) {
-            const int base = (rsub * cvn + cvl) * 8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                spart[0][base + j] = a0[j];
-                spart[1][base + j] = a1[j];
-                spart[2][base + j] = a3[j];
-            }
-        }
-        __syncthreads();
-        const int ncol = cvn * 8;                  // columns of this chunk
-        for (int c = threadIdx.x; c < ncol; c += 256) {
-            float s0 = 0.f, s1 = 0.f, s3 = 0.f;
-            for (int r = 0; r < RS; ++r) {
-                s0 += spart[0][r * ncol + c];
-                s1 += spart[1][r * ncol + c];
-                s3 += spart[2][r * ncol + c];
-            }
-            const int col = cvb * 8 + c;
-            float* part = p.part + (size_t)rb * (p.y2 ? 4 : 2) * p.C;      // this row block's row of the partials table
-            part[col] = s0;
-            part[p.C + col] = s1;
-            if (p.y2) {
-                part[2 * p.C + col] = s0;
-                part[3 * p.C + col] = s3;
-            }
-        }
-    }
-}
-
-// Specialised reduce for the launches without a forward multiplier (all but one BatchNorm of the network).  Same block /
-// thread mapping and the same fixed-order LDS combine as the generic kernel above, but (a) the per-channel constants are
-// loaded ONCE per thread instead of once per row, (b) the configuration flags are template parameters, so the row loop is
-// one basic block, and (c) U rows are in flight per thread: all of their 16-byte loads are issued before the first use
+// The reduce kernel.  A block owns ONE chunk of `chv` 8-channel vectors (up to 64 channels) and a range of rows; its 256 threads
+// are chv vector lanes x 256/chv row lanes.  The grid is chunks x row blocks with at most 64 row blocks, so a channel's partial
+// sums form a column of <= 64 entries that one small launch adds up in order (deterministic, no atomics).
+// Each thread owns one 8-channel vector and a strided subset of the block's rows (register accumulation, rows in the order
+// r0 + rsub, + RS, + 2 RS, ...); the RS row lanes of a vector are then combined through a plain LDS table + a column sum in lane
+// order.  (a) The per-channel constants are loaded ONCE per thread, (b) the configuration is a template parameter, so the row
+// loop is one basic block, and (c) U rows are in flight per thread: all of their 16-byte loads are issued before the first use
 // (rows past the block's range re-read its last row with weight 0 - an unconditional load, not a branch).
-//   MASK 0: no ReLU; 1: ReLU mask from the stored forward output z; 2: ReLU mask recomputed from scale*y + shift.
-template <int MASK, bool Y2, bool POOL>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_fast_kernel(const cris_bn_bwd_params p, int rows_per_block, int chv, int chunks) {
+//   MASK: bn_bwd_mask_mode;  Y2: second branch;  POOL: dz at half resolution;  MUL: dz times the forward's per-sample multiplier.
+template <int MASK, bool Y2, bool POOL, bool MUL>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const cris_bn_bwd_params p, int rows_per_block, int chv, int chunks) {
     constexpr int U = Y2 ? 2 : 4;
-    __shared__ float spart[3][256 * 8];
+    __shared__ float spart[3][256 * 8];            // [sum][thread-major: rsub * cvn*8 + cv_local*8 + j]
     const int CV = p.C >> 3;
     const int M = p.Bn * p.H * p.W;
     const int chunk = blockIdx.x % chunks, rb = blockIdx.x / chunks;
@@ -783,8 +731,10 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_fast_kernel(const cris_bn_b
             const bf16_t* dzb = p.dz + p.dz_coff + c0;
             const bf16_t* zb = MASK == 1 ? p.z + p.z_coff + c0 : nullptr;
             const bf16_t* y2b = Y2 ? p.y2 + p.y2_coff + c0 : nullptr;
+            const float* mub = MUL ? p.mul + c0 : nullptr;
             for (int m = r0 + rsub; m < r1; m += RS * U) {
                 uint4 ry[U], rdz[U], rz[U], ry2[U];
+                float4 rmu[U][2];
                 float wgt[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
@@ -802,6 +752,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_fast_kernel(const cris_bn_b
                     rdz[u] = *reinterpret_cast<const uint4*>(dzb + (size_t)mo * p.lddz);
                     if (MASK == 1) rz[u] = *reinterpret_cast<const uint4*>(zb + (size_t)mc * p.ldz);
                     if (Y2) ry2[u] = *reinterpret_cast<const uint4*>(y2b + (size_t)mc * p.ldy2);
+                    if (MUL) {                      // the multiplier row of the (clamped) row's sample
+                        const float4* q = reinterpret_cast<const float4*>(mub + (size_t)cris_div24(mc, HW, small_px) * p.C);
+                        rmu[u][0] = q[0];
+                        rmu[u][1] = q[1];
+                    }
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
@@ -810,15 +765,17 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_fast_kernel(const cris_bn_b
                     unpack8(rdz[u], dz);
                     if (MASK == 1) unpack8(rz[u], z);
                     if (Y2) unpack8(ry2[u], y2);
+                    if (MUL) {
+                        const float mu[8] = {rmu[u][0].x, rmu[u][0].y, rmu[u][0].z, rmu[u][0].w, rmu[u][1].x, rmu[u][1].y, rmu[u][1].z, rmu[u][1].w};
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) dz[j] *= mu[j];
+                    }
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        bool pos = true;
-                        if (MASK == 1) pos = z[j] > 0.f;
-                        if (MASK == 2) pos = (y[j] * sc[j] + sh[j]) > 0.f;
-                        const float g = pos ? dz[j] * wgt[u] : 0.f;
+                        const float g = bn_bwd_g(bn_bwd_pos(MASK, j, y, z, sc, sh), dz[j], wgt[u]);
                         a0[j] += g;
-                        a1[j] += g * ((y[j] - mean[j]) * inv[j]);
-                        if (Y2) a3[j] += g * ((y2[j] - mean2[j]) * inv2[j]);
+                        a1[j] += g * bn_xhat(j, y, mean, inv);
+                        if (Y2) a3[j] += g * bn_xhat(j, y2, mean2, inv2);
                     }
                 }
             }
@@ -833,7 +790,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_fast_kernel(const cris_bn_b
             }
         }
         __syncthreads();
-        const int ncol = cvn * 8;
+        const int ncol = cvn * 8;                  // columns of this chunk
         for (int c = threadIdx.x; c < ncol; c += 256) {
             float s0 = 0.f, s1 = 0.f, s3 = 0.f;
             for (int r = 0; r < RS; ++r) {
@@ -842,7 +799,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_fast_kernel(const cris_bn_b
                 if (Y2) s3 += spart[2][r * ncol + c];
             }
             const int col = cvb * 8 + c;
-            float* part = p.part + (size_t)rb * (Y2 ? 4 : 2) * p.C;
+            float* part = p.part + (size_t)rb * (Y2 ? 4 : 2) * p.C;      // this row block's row of the partials table
             part[col] = s0;
             part[p.C + col] = s1;
             if (Y2) {
@@ -853,20 +810,20 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_fast_kernel(const cris_bn_b
     }
 }
 
+// the instantiation of a launch the argument checks of bn_bwd_reduce_launch admitted: pooling goes with a plain BN (no second
+// branch, no multiplier) and never takes its mask from z; a second branch never recomputes its mask
 typedef void (*bn_bwd_reduce_fn)(const cris_bn_bwd_params, int, int, int);
-// [MASK][Y2][POOL]; combinations the path never produces stay on the generic kernel
-static bn_bwd_reduce_fn bn_bwd_reduce_fast_table(int mask, bool y2, bool pool) {
-    if (pool) {
-        if (y2 || mask == 1) return nullptr;
-        return mask == 2 ? bn_bwd_reduce_fast_kernel<2, false, true> : bn_bwd_reduce_fast_kernel<0, false, true>;
-    }
-    if (y2) {
-        if (mask == 2) return nullptr;
-        return mask == 1 ? bn_bwd_reduce_fast_kernel<1, true, false> : bn_bwd_reduce_fast_kernel<0, true, false>;
-    }
-    if (mask == 1) return bn_bwd_reduce_fast_kernel<1, false, false>;
-    if (mask == 2) return bn_bwd_reduce_fast_kernel<2, false, false>;
-    return bn_bwd_reduce_fast_kernel<0, false, false>;
+template <bool MUL>
+static bn_bwd_reduce_fn bn_bwd_reduce_pick(int mask, bool y2) {
+    if (y2) return mask == 1 ? bn_bwd_reduce_kernel<1, true, false, MUL> : bn_bwd_reduce_kernel<0, true, false, MUL>;
+    if (mask == 1) return bn_bwd_reduce_kernel<1, false, false, MUL>;
+    if (mask == 2) return bn_bwd_reduce_kernel<2, false, false, MUL>;
+    return bn_bwd_reduce_kernel<0, false, false, MUL>;
+}
+static bn_bwd_reduce_fn bn_bwd_reduce_pick(const cris_bn_bwd_params& p) {
+    const int mask = bn_bwd_mask_mode(p);
+    if (p.pool) return mask == 2 ? bn_bwd_reduce_kernel<2, false, true, false> : bn_bwd_reduce_kernel<0, false, true, false>;
+    return p.mul ? bn_bwd_reduce_pick<true>(mask, p.y2 != nullptr) : bn_bwd_reduce_pick<false>(mask, p.y2 != nullptr);
 }
 
 // gradient of the per-sample multiplier (FPN: f5 = relu(bn(y)) * state, model/layers.py:289): dmul[b][c] = sum over the pixels of
@@ -931,6 +888,18 @@ extern "C" long cris_bn_bwd_ws_floats(const cris_bn_bwd_params* p) {
     return (long)bn_bwd_geometry(p->Bn * p->H * p->W, p->C).rbs * (p->y2 ? 4 : 2) * p->C;
 }
 
+// the partial rows of `p.part`, added up in row order (deterministic) into the [2C] ([4C] with y2) `p.sums` (+=); with a link
+// the sums are exchanged inside the same launch (sum_partials_kernel)
+static int bn_bwd_sum_parts(const cris_bn_bwd_params& p, int nparts, float* local_sums, const cris_p2p_link& link, const char* fn,
+                            void* stream) {
+    const int ncol = (p.y2 ? 4 : 2) * p.C;
+    if (p2p_link_check(link, ncol, fn)) return -1;
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(cris_cdiv(ncol, 16)), dim3(256), 0, (hipStream_t)stream, p.part, nparts, ncol, p.sums,
+                       local_sums, link);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
 static int bn_bwd_reduce_launch(const cris_bn_bwd_params* pp, float* local_sums, const cris_p2p_link& link, void* stream) {
     const cris_bn_bwd_params& p = *pp;
     CRIS_CHECK_ARG(p.dz && p.y && p.mean && p.invstd && p.sums && p.part, "null operand");
@@ -940,23 +909,10 @@ static int bn_bwd_reduce_launch(const cris_bn_bwd_params* pp, float* local_sums,
     CRIS_CHECK_ARG(!p.pool || (p.scale && p.shift && !p.y2 && !p.mul), "pool backward needs scale/shift, plain BN");
     CRIS_CHECK_ARG(!p.mul || !p.dmul || (p.relu && !p.pool && !p.y2 && p.scale && p.shift && (p.lddz & 7) == 0 && (p.dz_coff & 7) == 0),
                    "multiplier gradient: plain BN + ReLU");
-    const int M = p.Bn * p.H * p.W;
-    const bn_bwd_geom g = bn_bwd_geometry(M, p.C);
-    static const int use_fast = cris_env_int("CRIS_BN_RED_FAST", 1);
-    bn_bwd_reduce_fn fast = nullptr;
-    if (use_fast && !p.mul && (p.ldy & 7) == 0 && (p.y_coff & 7) == 0 && (p.lddz & 7) == 0 && (p.dz_coff & 7) == 0 &&
-        (!p.y2 || ((p.ldy2 & 7) == 0 && (p.y2_coff & 7) == 0 && p.z))) {
-        const int mask = !p.relu ? 0 : (!p.pool && (p.y2 || p.z)) ? 1 : 2;
-        if (mask != 1 || ((p.ldz & 7) == 0 && (p.z_coff & 7) == 0)) fast = bn_bwd_reduce_fast_table(mask, p.y2 != nullptr, p.pool != 0);
-    }
-    hipLaunchKernelGGL(fast ? fast : bn_bwd_reduce_kernel, dim3(g.chunks * g.rbs), dim3(256), 0, (hipStream_t)stream, p, g.rpb, g.chv, g.chunks);
+    const bn_bwd_geom g = bn_bwd_geometry(p.Bn * p.H * p.W, p.C);
+    hipLaunchKernelGGL(bn_bwd_reduce_pick(p), dim3(g.chunks * g.rbs), dim3(256), 0, (hipStream_t)stream, p, g.rpb, g.chv, g.chunks);
     CRIS_LAUNCH_CHECK();
-    // the row blocks' partial rows, summed in block order (deterministic) into the [2C] ([4C]) sums (+=)
-    const int ncol = (p.y2 ? 4 : 2) * p.C;
-    if (p2p_link_check(link, ncol, __func__)) return -1;
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(cris_cdiv(ncol, 16)), dim3(256), 0, (hipStream_t)stream, p.part, g.rbs, ncol, p.sums,
-                       local_sums, link);
-    CRIS_LAUNCH_CHECK();
+    if (int rc = bn_bwd_sum_parts(p, g.rbs, local_sums, link, __func__, stream)) return rc;
     if (p.mul && p.dmul) {
         hipLaunchKernelGGL(bn_dmul_kernel, dim3(p.Bn * cris_cdiv(p.C >> 3, 8)), dim3(256), 0, (hipStream_t)stream, p);
         CRIS_LAUNCH_CHECK();
@@ -970,12 +926,7 @@ static int bn_bwd_sum_launch(const cris_bn_bwd_params* pp, int nparts, float* lo
     const cris_bn_bwd_params& p = *pp;
     CRIS_CHECK_ARG(p.sums && p.part && nparts > 0 && (p.C & 7) == 0, "bad args");
     CRIS_CHECK_ARG(!p.y2 && !p.mul, "partial rows from a GEMM epilogue exist for the plain conv -> BatchNorm -> ReLU chain only");
-    const int ncol = 2 * p.C;
-    if (p2p_link_check(link, ncol, __func__)) return -1;
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(cris_cdiv(ncol, 16)), dim3(256), 0, (hipStream_t)stream, p.part, nparts, ncol, p.sums,
-                       local_sums, link);
-    CRIS_LAUNCH_CHECK();
-    return 0;
+    return bn_bwd_sum_parts(p, nparts, local_sums, link, __func__, stream);
 }
 extern "C" int cris_bn_bwd_sum(const cris_bn_bwd_params* pp, int nparts, void* stream) {
     CRIS_CHECK_ARG(pp, "null argument");
@@ -1033,7 +984,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const cris_bn_bwd_par
 }
 
 // Fast path of the backward apply (same idea as bn_apply_fast_kernel: one 8-channel vector per thread, constants loaded once,
-// flags as template parameters, U rows in flight).  MASK as in bn_bwd_reduce_fast_kernel.
+// flags as template parameters, U rows in flight).  MASK: bn_bwd_mask_mode.
 template <int MASK, bool Y2>
 __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(const cris_bn_bwd_params p, int cv_shift) {
     constexpr int U = Y2 ? 2 : 4;
@@ -1088,11 +1039,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(const cris_bn_bw
             if (MASK == 1) unpack8(rz[u], z);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                bool pos = true;
-                if (MASK == 1) pos = z[j] > 0.f;
-                if (MASK == 2) pos = (y[j] * sc[j] + sh[j]) > 0.f;
-                g[j] = pos ? dz[j] : 0.f;
-                const float xh = (y[j] - mean[j]) * inv[j];
+                g[j] = bn_bwd_g(bn_bwd_pos(MASK, j, y, z, sc, sh), dz[j], 1.f);
+                const float xh = bn_xhat(j, y, mean, inv);
                 o[j] = sc[j] * (g[j] - a0[j] - xh * s1[j] * invc);
             }
             cris_st16(dyb + (size_t)mu * p.lddy, pack8(o));
@@ -1101,7 +1049,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(const cris_bn_bw
                 unpack8(ry2[u], y2);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const float xh2 = (y2[j] - mean2[j]) * inv2[j];
+                    const float xh2 = bn_xhat(j, y2, mean2, inv2);
                     o[j] = sc2[j] * (g[j] - a0[j] - xh2 * s3[j] * invc);
                 }
                 cris_st16(dy2b + (size_t)mu * p.lddy2, pack8(o));
@@ -1131,7 +1079,7 @@ extern "C" int cris_bn_bwd_apply(const cris_bn_bwd_params* pp, void* stream) {
                          (!p.y2 || ((p.ldy2 & 7) == 0 && (p.y2_coff & 7) == 0 && p.z && (!p.dy2 || ((p.lddy2 & 7) == 0 && (p.dy2_coff & 7) == 0)))) &&
                          (!p.dident || ((p.lddi & 7) == 0 && (p.di_coff & 7) == 0));
     if (use_fast && cvs >= 0 && !p.pool && !p.mul && aligned) {
-        const int mask = !p.relu ? 0 : (p.y2 || p.z) ? 1 : 2;            // the same rule as bn_bwd_point / cris_bn_bwd_reduce
+        const int mask = bn_bwd_mask_mode(p);
         if (mask != 1 || ((p.ldz & 7) == 0 && (p.z_coff & 7) == 0)) {
             const int grid = bn_fast_grid(total, p.y2 ? 2 : 4);
             typedef void (*fn_t)(const cris_bn_bwd_params, int);

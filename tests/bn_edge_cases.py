@@ -89,15 +89,20 @@ def bwd_mask(c):
     return 1 if not c["pool"] and (c.get("y2") is not None or c.get("z") is not None) else 2
 
 
-def reduce_path(c):
-    """every operand of these tests is 8-aligned, so only the flags decide"""
-    two, z, pool = c.get("y2") is not None, c.get("z") is not None, c["pool"]
-    if c.get("mul") is not None or (two and not z):
-        return "generic"
-    m = bwd_mask(c)
-    if (pool and (two or m == 1)) or (two and m == 2):
-        return "generic"
-    return "fast"
+def reduce_instance(c):
+    """(MASK, Y2, POOL, MUL) of the one reduce kernel the case launches"""
+    return bwd_mask(c), c.get("y2") is not None, bool(c["pool"]), c.get("mul") is not None
+
+
+# the instantiations the reduce launcher admits: pooling goes with a plain BatchNorm (no y2, no mul) and never takes its mask
+# from z; over two branches the mask is never recomputed
+REDUCE_INSTANCES = ({(m, False, True, False) for m in (0, 2)} | {(m, True, False, mul) for m in (0, 1) for mul in (False, True)} |
+                    {(m, False, False, mul) for m in (0, 1, 2) for mul in (False, True)})
+
+
+def wants_dmul(c):
+    """the reduce launcher computes the multiplier's gradient for a plain BatchNorm + ReLU only"""
+    return c.get("mul") is not None and c["relu"] and not c["pool"] and c.get("y2") is None
 
 
 def bwd_apply_path(c):
@@ -165,25 +170,26 @@ def plant_z(z):
 
 def make_bwd(variant, B, H, W, C, device="cpu", dident=None, dy2=True, count_factor=1):
     """variant: m0 / m2 (plain, ReLU off / recomputed mask), m1 (mask from z), pool_m0 / pool_m2, two_m0 (y2, no ReLU, no z),
-    two_m0z (the same with z passed), two_m1, mul_m2 (+ dmul).  dz, mean, invstd and the old / supplied sums are random."""
+    two_m0z (the same with z passed), two_m1, mul_m0 / mul_m1 / mul_m2 (per-sample multiplier on m0 / m1 / m2; dmul where
+    wants_dmul), two_mul_m0 / two_mul_m1 (the multiplier over two branches).  dz, mean, invstd and the old / supplied sums are random."""
     M = B * H * W
     act = lambda seed: grid_vals((B, H, W, C), seed, 2.0 ** -4, -8, 8, device)
     pool, two = variant.startswith("pool"), variant.startswith("two")
     OH, OW = (H // 2, W // 2) if pool else (H, W)
     c = dict(y=act(201), scale=grid_vals((C,), 202, 2.0 ** -3, -2, 2, device), shift=grid_vals((C,), 203, 2.0 ** -8, -2, 2, device, odd=True),
              mean=rand_f32((C,), 204, device), invstd=rand_invstd((C,), 205, device), dz=rand_bf((B, OH, OW, C), 206, device),
-             relu=variant not in ("m0", "pool_m0", "two_m0", "two_m0z"), pool=pool, count=float(M * count_factor))
+             relu=variant not in ("m0", "pool_m0", "two_m0", "two_m0z", "mul_m0", "two_mul_m0"), pool=pool, count=float(M * count_factor))
     ncol = (4 if two else 2) * C
     c["sums_old"] = rand_f32((ncol,), 207, device, scale=4.0)                        # reduce: += into these
     c["sums"] = rand_f32((ncol,), 208, device, scale=(M * count_factor) ** 0.5)     # apply: the supplied batch totals
-    if variant in ("m1", "two_m1", "two_m0z"):
+    if variant in ("m1", "two_m1", "two_m0z", "mul_m1", "two_mul_m1"):
         c["z"] = plant_z(rand_bf((B, H, W, C), 209, device))
         c["dz"].view(-1, C)[0, :4] = 4.0                                             # a wrong decision there is no rounding error
         c["dz"].view(-1, C)[-1, C - 4:] = 4.0
     if two:
         c.update(y2=act(210), mean2=rand_f32((C,), 211, device), invstd2=rand_invstd((C,), 212, device),
                  scale2=grid_vals((C,), 213, 2.0 ** -3, -2, 2, device), want_dy2=bool(dy2))
-    if variant == "mul_m2":
+    if "mul" in variant:
         c["mul"] = grid_vals((B, C), 214, 2.0 ** -2, 0, 4, device)
     if dident is not None:
         c["dident"] = dident                                                         # "store" or "accum"
@@ -506,6 +512,9 @@ REDUCE_C = [8, 40, 72, 136, 280, 2048, 8192]
 REDUCE_M = [1, 31, 33, 65, 2049]
 REDUCE_M_RAGGED = {8: 65927}                     # rpb = 1031: a second, ragged trip of RS * U = 1024 rows
 POOL_SHAPES = [(1, 2, 2), (2, 4, 6), (3, 26, 26)]
+# M = 65933, rpb = 1031 as REDUCE_M_RAGGED; HW = 9419 is no multiple of 256, so sample boundaries fall inside a group of in-flight
+# rows and inside row blocks
+REDUCE_MUL_RAGGED = (7, 9419, 1, 8)
 
 
 def reduce_cases():
@@ -530,13 +539,22 @@ def reduce_cases():
     for C in (40, 72):                                                               # CV = 5, 9
         for (H, W) in ((1, 1), (3, 11), (10, 10)):
             add("mul_m2", 3, H, W, C)
+    # the multiplier through the U-unrolled row loop.  M = 99 in row blocks of 32, no more than the RS row lanes (256 at C = 8, 128 at
+    # C = 64, 32 and - in its 3-vector last chunk - 85 at C = 280): every in-flight row after the first is a clamped re-read of the
+    # block's last row, which can lie in another sample (HW = 33) than the row it stands in for
+    for C in (8, 64, 280):
+        add("mul_m2", 3, 11, 3, C)
+    add("mul_m2", *REDUCE_MUL_RAGGED)
+    for variant in ("mul_m0", "mul_m1", "two_mul_m0", "two_mul_m1"):
+        for C in (8, 280):
+            add(variant, 3, 11, 3, C)
     return out
 
 
 # sentinel rows: (id, variant, (B, H, W, C)) - few row blocks, so that every block's first and last row gets a launch
 SENTINEL_CASES = [("m2-c64", "m2", (1, 100, 1, 64)), ("m1-c64", "m1", (1, 100, 1, 64)), ("m2-c280", "m2", (1, 130, 1, 280)),
                   ("m0-c2048", "m0", (1, 300, 1, 2048)), ("pool_m2-c64", "pool_m2", (2, 6, 10, 64)), ("pool_m2-c280", "pool_m2", (2, 6, 10, 280)),
-                  ("two_m1-c64", "two_m1", (1, 100, 1, 64))]
+                  ("two_m1-c64", "two_m1", (1, 100, 1, 64)), ("mul_m2-c64", "mul_m2", (2, 50, 1, 64))]
 
 
 def sentinel_rows(M, C):

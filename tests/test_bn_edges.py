@@ -4,11 +4,11 @@ The launchers are called directly (cris_bn_apply, cris_bn_bwd_reduce, cris_bn_bw
 with scale / shift / mean / invstd / sums / z supplied by the test, so that a stage's inputs are exact and not another kernel's
 output.  Every output lives in a Slab of guard bits that must survive, every input in a Slab of NaN guards, and every operand of
 a call has its own leading dimension and column offset.  Statements, bounds and case tables: tests/bn_edge_cases.py; that a
-plain fp32 evaluation meets the same checks, and that every case reaches the path it is named for: tests/test_bn_edges_cpu.py.
+plain fp32 evaluation meets the same checks, and that every case reaches the kernel it is named for: tests/test_bn_edges_cpu.py.
 
 Group A: the forward on grid inputs, bit for bit.  Group B: the backward stage by stage (reduce, sentinel rows, the summation
 of hand-made partial tables, apply with supplied sums, end to end through ops.bn_bwd).  Group C (last): the two sides of 2^24
-work items of the generic kernels."""
+work items of the generic apply kernels."""
 import ctypes as C
 
 import pytest
@@ -136,7 +136,7 @@ def reduce_outputs(p, keep, c, sums_init):
     keep["sums"] = vec(sums_init, nan_guard=False)
     keep["part"] = Slab(rbs, ncol, F32, DEV)
     p.sums, p.part = hip.ptr(keep["sums"].rows), hip.ptr(keep["part"].rows)
-    if c.get("mul") is not None:
+    if N.wants_dmul(c):
         keep["dmul"] = Slab(B, C_, F32, DEV)
         p.dmul = hip.ptr(keep["dmul"].rows)
 
@@ -162,7 +162,8 @@ def test_bn_bwd_reduce_sentinel_rows(variant, shape):
     """dz is zero except for one (pooled) row of ones: sum g must be that row's mask exactly - a dropped row gives 0, a row
     counted twice (the clamped re-read with a weight) gives 2 - and sum g xhat that row's xhat to two roundings (2^-22 relative).
     A pooled row feeds four rows: 0.25 x their masks, exact, and 0.25 x the sum of their xhat, four terms of two roundings each
-    and three additions, bounded by 2^-21 of the sum of magnitudes."""
+    and three additions, bounded by 2^-21 of the sum of magnitudes.  With a multiplier the row's g is mask x mul[b] of its sample
+    b: a quarter of a small integer times one, exact; its product with xhat is a third rounding, still within 2^-22."""
     B, H, W, C_ = shape
     M = B * H * W
     c = N.make_bwd(variant, *shape)
@@ -171,6 +172,8 @@ def test_bn_bwd_reduce_sentinel_rows(variant, shape):
     reduce_outputs(p, keep, c, torch.zeros_like(c["sums_old"]))
     mask = N.relu_mask(c, F64)
     mask = torch.ones(M, C_, dtype=F64) if mask is None else mask.reshape(M, C_).double()
+    if c.get("mul") is not None:
+        mask = mask * c["mul"].double().repeat_interleave(H * W, 0)
     xh = [N.xhat(c, F64)] + ([N.xhat(c, F64, second=True)] if two else [])
     rows = N.sentinel_rows(M, C_)
     assert 2 <= len(rows) <= 48
@@ -279,7 +282,7 @@ def test_bn_bwd_end_to_end(variant, dident, shape):
 
 def test_relu_over_two_branches_needs_z():
     """relu + y2 without z has no mask source (it cannot be recomputed from one branch): both launchers refuse it before any
-    launch; without ReLU the same operands are accepted (the generic kernels: the reduce and apply cases `two_m0`)"""
+    launch; without ReLU the same operands are accepted (MASK 0 reads no z: the reduce and apply cases `two_m0`)"""
     shape = (1, 33, 1, 64)
     c = N.make_bwd("two_m0", *shape)
     p, keep = bwd_setup(c)

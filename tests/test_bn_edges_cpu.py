@@ -1,8 +1,8 @@
 """What tests/test_bn_edges.py rests on, without a GPU: (1) on the grid inputs a plain fp32 evaluation of the forward bit-equals
 the float64 one after the bf16 rounding - the exactness claim; (2) the fp32 evaluation of every bounded statement meets the
 bound the GPU test applies to the kernels, through the same check functions; (3) the Python mirrors of bn_cv_shift,
-bn_fast_grid and bn_bwd_geometry put every case on the path it is named for; (4) the checks refuse the wrong results they
-exist to catch."""
+bn_fast_grid, bn_bwd_geometry and bn_bwd_mask_mode put every case on the kernel (instantiation) it is named for; (4) the checks
+refuse the wrong results they exist to catch."""
 import pytest
 import torch
 
@@ -57,7 +57,7 @@ def test_planted_mask_values():
 def test_reduce_bound_admits_fp32(variant, shape):
     c = N.make_bwd(variant, *shape)
     N.check_sums(N.bn_bwd_sums(c, F32), c, "fp32 evaluation")
-    if c.get("mul") is not None:
+    if N.wants_dmul(c):
         N.check_dmul(N.bn_bwd_dmul(c, F32), c, "fp32 evaluation")
 
 
@@ -152,15 +152,22 @@ def test_grid_boundary_cases():
 
 
 def test_reduce_cases_reach_their_kernels():
-    want = {"m0": "fast", "m1": "fast", "m2": "fast", "pool_m0": "fast", "pool_m2": "fast", "two_m0": "generic", "two_m0z": "fast",
-            "two_m1": "fast", "mul_m2": "generic"}
-    masks = {"m0": 0, "m1": 1, "m2": 2, "pool_m0": 0, "pool_m2": 2, "two_m0": 0, "two_m0z": 0, "two_m1": 1, "mul_m2": 2}
-    seen = set()
+    """(MASK, Y2, POOL, MUL) of the one reduce kernel, per variant; every instantiation the launcher admits has a case"""
+    want = {"m0": (0, False, False, False), "m1": (1, False, False, False), "m2": (2, False, False, False),
+            "pool_m0": (0, False, True, False), "pool_m2": (2, False, True, False), "two_m0": (0, True, False, False),
+            "two_m0z": (0, True, False, False), "two_m1": (1, True, False, False), "mul_m0": (0, False, False, True),
+            "mul_m1": (1, False, False, True), "mul_m2": (2, False, False, True), "two_mul_m0": (0, True, False, True),
+            "two_mul_m1": (1, True, False, True)}
+    dmul = {"mul_m1", "mul_m2"}                                      # the multiplier's gradient: plain BatchNorm + ReLU
+    seen, reached = set(), set()
     for name, variant, shape in _REDUCE:
         c = N.make_bwd(variant, shape[0], 2, 2, 8)                   # the flags decide, not the shape
-        assert N.reduce_path(c) == want[variant] and N.bwd_mask(c) == masks[variant], name
+        assert N.reduce_instance(c) == want[variant] and N.bwd_mask(c) == want[variant][0], name
+        assert N.wants_dmul(c) == (variant in dmul), name
         seen.add(variant)
+        reached.add(N.reduce_instance(c))
     assert seen == set(want)
+    assert reached == N.REDUCE_INSTANCES and len(N.REDUCE_INSTANCES) == 12
     plain = {(s[3], s[1]) for _, v, s in _REDUCE if v == "m2"}
     assert {(C, M) for C in N.REDUCE_C for M in N.REDUCE_M} <= plain
     assert {N.bwd_geometry(33, C)["last_cvn"] for C in N.REDUCE_C} == {1, 3, 8}
@@ -170,18 +177,32 @@ def test_reduce_cases_reach_their_kernels():
     assert g["rpb"] == 1031 and g["rpb"] % (256 * 4) and g["rpb"] % (256 * 2) and g["rpb"] > 256 * 4
     g = N.bwd_geometry(2049, 2048)
     assert g["rpb"] == 129 and g["rpb"] % (32 * 4) == 1
-    assert {(s[0], s[1] * s[2], s[3] >> 3) for _, v, s in _REDUCE if v == "mul_m2"} == {(3, hw, cv) for hw in (1, 33, 100) for cv in (5, 9)}
+    mul = {(s[0], s[1] * s[2], s[3] >> 3) for _, v, s in _REDUCE if v == "mul_m2"}
+    assert mul == {(3, hw, cv) for hw in (1, 33, 100) for cv in (5, 9)} | {(3, 33, cv) for cv in (1, 8, 35)} | {(7, 9419, 1)}
+    for C, rs in ((8, {256}), (64, {128}), (280, {32, 85})):                        # row lanes of the full chunks / the last chunk
+        g = N.bwd_geometry(99, C)
+        assert {256 // g["chv"], 256 // g["last_cvn"]} == rs and g["rpb"] == 32 <= min(rs), "no second in-flight row inside a block"
+    B, H, W, C = N.REDUCE_MUL_RAGGED
+    g = N.bwd_geometry(B * H * W, C)
+    assert B * H * W == 65933 and g["rpb"] == 1031 and (H * W) % 256 and (H * W) % g["rpb"]
+    for variant in ("mul_m0", "mul_m1", "two_mul_m0", "two_mul_m1"):
+        assert {s for _, v, s in _REDUCE if v == variant} == {(3, 11, 3, 8), (3, 11, 3, 280)}
 
 
 def test_sentinel_cases():
+    inst = set()
     for name, variant, (B, H, W, C) in N.SENTINEL_CASES:
         M = B * H * W
         rows = N.sentinel_rows(M, C)
         blocks = N.row_blocks(M, C)
         assert len(blocks) >= 3 and blocks[-1][1] == M and len(rows) <= 48, name
         assert all(r0 in rows and r1 - 1 in rows for r0, r1 in blocks)
-        assert N.reduce_path(N.make_bwd(variant, B, 2, 2, 8)) == "fast"
+        inst.add(N.reduce_instance(N.make_bwd(variant, B, 2, 2, 8)))
+    assert inst == {(2, False, False, False), (1, False, False, False), (0, False, False, False), (2, False, True, False),
+                    (1, True, False, False), (2, False, False, True)}
     assert {C for _, _, (_, _, _, C) in N.SENTINEL_CASES} >= {64, 280}
+    (B, H, W, C), = [s for _, v, s in N.SENTINEL_CASES if v == "mul_m2"]
+    assert any(r0 < H * W < r1 for r0, r1 in N.row_blocks(B * H * W, C)), "a sample boundary inside a row block"
 
 
 def test_apply_cases_reach_their_kernels():
@@ -200,7 +221,7 @@ def test_apply_cases_reach_their_kernels():
         small, big = N.fast_ladder(C)
         assert {s[1] for n, v, d, y, f, s in _APPLY if s[3] == C and s[0] == s[2] == 1} == set(small) | {big}
     assert {i[5] for i in generic} == {24, 40, 280, 64}
-    assert any(i[0] and i[1] == 0 for i in generic), "y2, no ReLU, no z: the generic kernel"
+    assert any(i[0] and i[1] == 0 for i in generic), "y2, no ReLU, no z: the generic apply kernel"
 
 
 def test_div24_cases():

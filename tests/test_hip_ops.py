@@ -731,7 +731,8 @@ def test_bn_finalize_and_running_stats():
 @pytest.mark.parametrize("variant", ["plain", "pool", "ident", "two", "mul"])
 def test_bn_apply_and_backward(variant, shape):
     """C = 48: the generic kernels (C/8 not a power of two); C = 64 / 2048: the fast apply kernels (one channel vector per thread) -
-    one row per thread at M = 300 / 72, several passes with a ragged last one at M = 40000; pool / mul always take the generic ones"""
+    one row per thread at M = 300 / 72, several passes with a ragged last one at M = 40000; pool / mul always take the generic apply
+    ones (the backward reduce is one kernel for every C and variant)"""
     B, H, W, C_ = shape
     y, gamma, beta = _bn_setup(B, H, W, C_)
     y2d = y.reshape(-1, C_)
