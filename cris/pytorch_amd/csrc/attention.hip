@@ -162,18 +162,17 @@ static int attn_check(const cris_attn_params& p) {
 __global__ void attn_fwd_lds_kernel(const cris_attn_params p);
 __global__ void attn_bwd_dq_lds_kernel(const cris_attn_params p);
 __global__ void attn_bwd_dkv_lds_kernel(const cris_attn_params p);
-#ifndef AL_WAVES
 #define AL_WAVES 4                         // waves per block
-#endif
-#ifndef AL_G
-#define AL_G 1                             // 16-row groups per wave: a block covers 16 * AL_G * AL_WAVES = 64 rows
-#endif
+// 16-row groups per wave: a block covers 16 * AL_G * AL_WAVES = 64 rows.  Fixed at 1 since round 3; the kernels keep their
+// one-trip `g` loops and [AL_G] arrays because hipcc emits other code for them once the loops are written out
+// (profiles/strip_scaffolding.md), and these kernels have no per-element edge test that would cover a change.
+#define AL_G 1
 #define AL_LDS_FWD (3 * 2 * 8192)
 #define AL_LDS_DQ (2 * 3 * 8192)
 #define AL_LDS_DKV (2 * (4 * 8192 + 512))
 static bool attn_use_lds(const cris_attn_params& p, int loop_rows, bool key_mask_ok = false) {
-    static const int lds_min = cris_env_int("CRIS_ATTN_LDS_MIN", 384);
-    return !p.causal && (key_mask_ok || !p.key_tokens) && loop_rows >= lds_min && (p.Lk_pad & 7) == 0 && ((uintptr_t)p.Q & 15) == 0 &&
+    constexpr int ATTN_LDS_MIN = 384;       // fewest rows of the loop that take the LDS kernels
+    return !p.causal && (key_mask_ok || !p.key_tokens) && loop_rows >= ATTN_LDS_MIN && (p.Lk_pad & 7) == 0 && ((uintptr_t)p.Q & 15) == 0 &&
            ((uintptr_t)p.K & 15) == 0 && ((uintptr_t)p.V & 15) == 0 && (size_t)p.B * p.Lk * p.ldk * 2 < (1UL << 31) &&
            (size_t)p.B * p.Lq * p.ldq * 2 < (1UL << 31) && (size_t)p.B * p.Hn * 64 * (p.Lk_pad > p.Lq_pad ? p.Lk_pad : p.Lq_pad) * 2 < (1UL << 31);
 }
@@ -494,10 +493,10 @@ __global__ __launch_bounds__(64 * AL_WAVES) void attn_fwd_lds_kernel(const cris_
     const int b = bh / p.Hn, h = bh - b * p.Hn;
     const int q0w = bx * (16 * AL_G * AL_WAVES) + wave * (16 * AL_G);
 
-    int q[2];
-    bool qok[2];
-    bf16x8 bq[2][2];
-    uint32_t didx0[2];
+    int q[AL_G];
+    bool qok[AL_G];
+    bf16x8 bq[AL_G][2];
+    uint32_t didx0[AL_G];
 #pragma unroll
     for (int g = 0; g < AL_G; ++g) {
         q[g] = q0w + g * 16 + fr;
@@ -524,12 +523,12 @@ __global__ __launch_bounds__(64 * AL_WAVES) void attn_fwd_lds_kernel(const cris_
     const uint32_t dkey = cris_drop_key(p.drop_seed + (p.drop_seed_dev ? p.drop_seed_dev[0] : 0u), p.drop_stream);
     const float inv_keep = has_drop ? 1.f / (1.f - p.drop_p) : 1.f;
     // pre-mixed hash word of (query row, key fg*8) per group; key k0 + j adds (k0 + j) * CRIS_DROP_MUL (see cris_keep_h)
-    uint32_t dh0[2];
+    uint32_t dh0[AL_G];
 #pragma unroll
     for (int g = 0; g < AL_G; ++g) dh0[g] = (didx0[g] + (uint32_t)(fg * 8)) * CRIS_DROP_MUL + dkey;
 
-    f32x4 o[2][4];
-    float m_run[2], l_run[2];
+    f32x4 o[AL_G][4];
+    float m_run[2], l_run[2];                   // (one entry per group would do: sized 2, hipcc emits the instruction order measured in round 3)
 #pragma unroll
     for (int g = 0; g < AL_G; ++g) {
         m_run[g] = NEG_INF;
@@ -657,11 +656,11 @@ __global__ __launch_bounds__(64 * AL_WAVES) void attn_bwd_dq_lds_kernel(const cr
     const int b = bh / p.Hn, h = bh - b * p.Hn;
     const int q0w = bx * (16 * AL_G * AL_WAVES) + wave * (16 * AL_G);
 
-    int q[2];
-    bool qok[2];
-    bf16x8 bq[2][2], bd[2][2];
-    float delta[2], lse[2];
-    uint32_t didx0[2];
+    int q[AL_G];
+    bool qok[AL_G];
+    bf16x8 bq[AL_G][2], bd[AL_G][2];
+    float delta[AL_G], lse[AL_G];
+    uint32_t didx0[AL_G];
 #pragma unroll
     for (int g = 0; g < AL_G; ++g) {
         q[g] = q0w + g * 16 + fr;
@@ -710,10 +709,10 @@ __global__ __launch_bounds__(64 * AL_WAVES) void attn_bwd_dq_lds_kernel(const cr
     const uint32_t dkey = cris_drop_key(p.drop_seed + (p.drop_seed_dev ? p.drop_seed_dev[0] : 0u), p.drop_stream);
     const float inv_keep = has_drop ? 1.f / (1.f - p.drop_p) : 1.f;
 
-    uint32_t dh0[2];                              // pre-mixed hash words, as in the forward kernel
+    uint32_t dh0[AL_G];                              // pre-mixed hash words, as in the forward kernel
 #pragma unroll
     for (int g = 0; g < AL_G; ++g) dh0[g] = (didx0[g] + (uint32_t)(fg * 8)) * CRIS_DROP_MUL + dkey;
-    f32x4 dq[2][4];
+    f32x4 dq[AL_G][4];
 #pragma unroll
     for (int g = 0; g < AL_G; ++g)
 #pragma unroll
@@ -806,9 +805,9 @@ __global__ __launch_bounds__(64 * AL_WAVES) void attn_bwd_dkv_lds_kernel(const c
     const int b = bh / p.Hn, h = bh - b * p.Hn;
     const int k0w = bx * (16 * AL_G * AL_WAVES) + wave * (16 * AL_G);
 
-    int key[2];
-    bool kok[2], kpad[2];
-    bf16x8 bk[2][2], bv[2][2];
+    int key[AL_G];
+    bool kok[AL_G], kpad[AL_G];
+    bf16x8 bk[AL_G][2], bv[AL_G][2];
 #pragma unroll
     for (int g = 0; g < AL_G; ++g) {
         key[g] = k0w + g * 16 + fr;
@@ -853,14 +852,14 @@ __global__ __launch_bounds__(64 * AL_WAVES) void attn_bwd_dkv_lds_kernel(const c
     // dropout index of (query qq, key) = (bh*Lq + qq)*Lk + key with qq = q0 + fg*8 + j: the pre-mixed word of (fg*8, key) per
     // group; q0 + j adds (q0 + j) * (Lk * CRIS_DROP_MUL), a scalar
     const uint32_t LkM = (uint32_t)p.Lk * CRIS_DROP_MUL;
-    uint32_t dh0[2];
-    bool kvalid[2];
+    uint32_t dh0[AL_G];
+    bool kvalid[AL_G];
 #pragma unroll
     for (int g = 0; g < AL_G; ++g) {
         dh0[g] = (((uint32_t)bh * (uint32_t)p.Lq + (uint32_t)(fg * 8)) * (uint32_t)p.Lk + (uint32_t)key[g]) * CRIS_DROP_MUL + dkey;
         kvalid[g] = kok[g] && !kpad[g];
     }
-    f32x4 dk[2][4], dv[2][4];
+    f32x4 dk[AL_G][4], dv[AL_G][4];
 #pragma unroll
     for (int g = 0; g < AL_G; ++g)
 #pragma unroll

@@ -700,8 +700,7 @@ extern "C" int cris_dynconv_fwd(const cris_bf16* x, int Bn, int H, int W, int C,
     const int LP = C / 8;
     CRIS_CHECK_ARG(x && wb && pred && !(C & 7) && LP >= 1 && LP <= 64 && (LP & (LP - 1)) == 0, "C/8 must be a power of two <= 64");
     // pixels per block: every block first gathers its 72 weights per lane (strided reads), so few pixels per block is mostly prologue
-    static const int ppb_env = cris_env_int("CRIS_DYNCONV_PPB", 128);     // (call r05e: 64 -> 128: -0.03 ms per step; 256: level)
-    const int ppb = ppb_env;
+    constexpr int ppb = 128;                                              // (call r05e: 64 -> 128: -0.03 ms per step; 256: level)
     dim3 grid(cris_cdiv(H * W, ppb), Bn);
     hipLaunchKernelGGL(dynconv_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, H, W, C, wb, ldwb, pred, ppb);
     CRIS_LAUNCH_CHECK();
@@ -783,9 +782,7 @@ __global__ __launch_bounds__(256) void dynconv_bwd_kernel(const bf16_t* __restri
     for (int i = threadIdx.x; i < ldwb; i += 256) part[i] = i < C * 9 + 1 ? sdw[i] : 0.f;      // padding columns: zeros
 }
 
-#ifndef DYNCONV_BWD_PPB
 #define DYNCONV_BWD_PPB 128                       // pixels per block: 85 x B blocks at 104 x 104 (was 512: 22 x B blocks, 89 us)
-#endif
 static int dynconv_bwd_blocks(int HW) { return cris_cdiv(HW, DYNCONV_BWD_PPB); }
 extern "C" long cris_dynconv_bwd_ws_floats(int Bn, int H, int W, int ldwb) { return (long)dynconv_bwd_blocks(H * W) * Bn * ldwb; }
 void cris_launch_sum_partials(const float* part, int nparts, int ncol, float* out, hipStream_t stream);      // norm.hip
@@ -1082,9 +1079,7 @@ extern "C" int cris_train_metric(const float* logits, const float* target, int B
 // ------------------------------------------------------------------------------------------------
 // fused multi-tensor Adam (torch.optim.Adam, non-amsgrad)
 // ------------------------------------------------------------------------------------------------
-#ifndef ADAM_ELEMS
-#define ADAM_ELEMS 8192
-#endif
+#define ADAM_ELEMS 8192                           // elements of a tensor per block
 #define AP_T 64                                   // packed tensors: a block owns AP_TN output rows x 64 input channels x all taps
 #define AP_TN(PT) ((PT) == 9 ? 32 : 64)           // 9 taps: 32 rows (37 KB of LDS, four blocks per CU; 64 rows = 74 KB, two blocks, ran
                                                   // the table at 3.4 TB/s against 5.7 for the 1-tap one)

@@ -10,37 +10,7 @@
 //   panel).  M <= 144 linear problems (text encoder, per-sample vectors) take a latency-oriented kernel: no staging, K
 //   split over the waves, deterministic LDS reduction.  No atomics anywhere.
 #include "gemm_common.h"
-// LDS-DMA ring depth per tile variant (K-steps in flight = depth - 1); -D switches for the A/B in profiles/r02_ab_experiments.md
-#ifndef ST_64x64
-#define ST_64x64 3
-#endif
-#ifndef ST_64x128
-#define ST_64x128 3
-#endif
-#ifndef ST_128x64
-#define ST_128x64 3
-#endif
-#ifndef ST_128x128
-#define ST_128x128 2
-#endif
 #define SKINNY_MAX_M 144      // M <= this and a 1x1 geometry -> skinny kernel (no LDS staging, K split over the waves)
-
-// Phase stamps of the 4-wave tile (tools/probe/gemm4_probe.hip compiles this file with -DG4_PROBE; the library never does): the
-// shader clock (s_memtime) of wave 0 of every block at  0 entry, 1 prologue DMAs issued, 2 first K-step landed (first barrier
-// passed), 3 K loop done, 4 epilogue stores issued, 5 stores acknowledged - kept in SGPRs and written once at the end, so the
-// counted vmcnt waits of the loop see no extra memory operation.  G4_ABL: pieces compiled out (results wrong by construction):
-// 1 no MFMAs, 2 no DMA refills inside the loop, 4 no epilogue, 8 nothing at all (the launch floor of this grid / LDS size).
-#ifdef G4_PROBE
-__device__ unsigned long long* g4_stamps;       // [blocks][8]
-#define G4_T(k) t_stamp[k] = __builtin_amdgcn_s_memtime()
-#ifndef G4_ABL
-#define G4_ABL 0
-#endif
-#else
-#define G4_T(k)
-#define G4_ABL 0
-#endif
-
 
 // ------------------------------------------------------------------------------------------------
 // forward / dgrad (4-wave tiles; lds_off and gemm_epilogue live in gemm_common.h)
@@ -77,14 +47,6 @@ __device__ __forceinline__ void conv_gemm_tile(const cris_conv_gemm_params& p, i
     constexpr int A_BYTES = BM * 128;
     constexpr int STAGE_BYTES = (BM + BN) * 128;
 
-#ifdef G4_PROBE
-    unsigned long long t_stamp[6];
-#endif
-    G4_T(0);
-    if (G4_ABL & 8) {                               // (probe: the launch alone - same grid, LDS size and kernel arguments, no work)
-        if (p.M < 0) p.colsum[0] = 0.f;
-        return;
-    }
     const int t = threadIdx.x;
     const int lane = t & 63;
     const int wave = (t >> 6) & 3;             // role inside the group of four (DMA rows, wave tile)
@@ -248,20 +210,14 @@ __device__ __forceinline__ void conv_gemm_tile(const cris_conv_gemm_params& p, i
         // prologue: STAGES-1 K-steps in flight (steps beyond nk read zeros: keeps the vmcnt arithmetic uniform)
 #pragma unroll
         for (int s = 0; s < STAGES - 1; ++s) issue_stage(s);
-        G4_T(1);
         int buf = 0;
         const int nkg = (nk + KS - 1) / KS;              // K-steps per group (a group's steps beyond nk read zeros)
         for (int kt = 0; kt < nkg; ++kt) {
             CRIS_VMCNT((STAGES - 2) * (NA + NB));       // this wave's share of K-step kt has landed ...
             __builtin_amdgcn_s_barrier();               // ... and everyone's; everyone is also done reading step kt-1
-#ifdef G4_PROBE
-            if (kt == 0) G4_T(2);
-#endif
-            if (!(G4_ABL & 2) || kt == 0) {
-                int nb = buf + STAGES - 1;
-                if (nb >= STAGES) nb -= STAGES;
-                issue_stage(nb);                        // refill the buffer of step kt-1 with step kt+STAGES-1
-            }
+            int nb = buf + STAGES - 1;
+            if (nb >= STAGES) nb -= STAGES;
+            issue_stage(nb);                            // refill the buffer of step kt-1 with step kt+STAGES-1
             const unsigned char* sa = ring + buf * STAGE_BYTES;
             const unsigned char* sb = sa + A_BYTES;
 #pragma unroll
@@ -281,9 +237,7 @@ __device__ __forceinline__ void conv_gemm_tile(const cris_conv_gemm_params& p, i
                 for (int i = 0; i < FM; ++i)
 #pragma unroll
                     for (int j = 0; j < FN; ++j) {
-                        if (G4_ABL & 1) {               // (probe ablation: keep the fragment reads alive without the MFMA)
-                            acc[i][j][0] += (float)af[i][0] + (float)bfr[j][0];
-                        } else if constexpr (MT == 32) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+                        if constexpr (MT == 32) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
                         else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
                     }
             }
@@ -292,7 +246,6 @@ __device__ __forceinline__ void conv_gemm_tile(const cris_conv_gemm_params& p, i
         }
     }
     CRIS_VMCNT(0);                                  // drain the (out-of-range) tail DMAs before the block retires
-    G4_T(3);
 
     if constexpr (KS > 1) {
         // group 1's partial sums -> LDS (over the drained rings) -> group 0: acc(even K-steps) + acc(odd K-steps)
@@ -316,24 +269,7 @@ __device__ __forceinline__ void conv_gemm_tile(const cris_conv_gemm_params& p, i
 #pragma unroll
                 for (int r = 0; r < NR; ++r) acc[i][j][r] += xch[(i * FN + j) * NR + r];
     }
-    if (!(G4_ABL & 4)) gemm_epilogue<EPI, MT, FM, FN>(p, acc, m0 + wm * WTM, n0 + wn * WTN, tile_m * WAVES_M + wm, lane);
-#ifdef G4_PROBE
-    if (G4_ABL & 4) {                               // keep the accumulators alive
-        float sink = 0.f;
-        for (int i = 0; i < FM; ++i)
-            for (int j = 0; j < FN; ++j) sink += acc[i][j][0] + acc[i][j][7];
-        if (sink == 123.456f) p.colsum[0] = sink;
-    }
-    G4_T(4);
-    CRIS_VMCNT(0);
-    G4_T(5);
-    if (t == 0 && g4_stamps) {
-        unsigned long long* d = g4_stamps + (size_t)blockIdx.x * 8;
-        for (int k = 0; k < 6; ++k) d[k] = t_stamp[k];
-        d[6] = __builtin_amdgcn_s_getreg((31 << 11) | 20);      // HW_REG_XCC_ID
-        d[7] = __builtin_amdgcn_s_getreg((31 << 11) | 4);       // HW_REG_HW_ID
-    }
-#endif
+    gemm_epilogue<EPI, MT, FM, FN>(p, acc, m0 + wm * WTM, n0 + wn * WTN, tile_m * WAVES_M + wm, lane);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int STAGES, int EPI, int MT_ = 32, int KS = 1>
@@ -363,9 +299,7 @@ __global__ __launch_bounds__(256) void conv_gemm_group_kernel(const cris_conv_ge
 // 512-B runs); fragments go straight from L2/HBM into registers (no LDS staging, no barrier in the loop), two K-chunks
 // per trip with all loads issued before the first MFMA; the partial accumulators are summed through LDS in a fixed wave
 // order (deterministic); full epilogue by wave 0.
-#ifndef SK_WAVES
 #define SK_WAVES 8
-#endif
 template <int FM>
 __global__ __launch_bounds__(64 * SK_WAVES) void skinny_gemm_kernel(const cris_conv_gemm_params p) {
     constexpr int FN = 2;
@@ -558,10 +492,10 @@ __global__ __launch_bounds__(256) void skinny_finish_kernel(const cris_conv_gemm
 }
 
 // K slices of the split-K skinny launch: enough blocks for the chip, at least 128 of K per slice
+constexpr int SKINNY_BLOCKS = 192;                 // blocks a split-K skinny launch aims for
 static int skinny_split_slices(const cris_conv_gemm_params& p) {
-    static const int target = cris_env_int("CRIS_SKINNY_BLOCKS", 192);
     const int nblocks = cris_cdiv(p.N, 32);
-    int ks = target / nblocks;
+    int ks = SKINNY_BLOCKS / nblocks;
     const int kmax = p.K / 128;
     if (ks > kmax) ks = kmax;
     if (ks < 1) ks = 1;
@@ -574,7 +508,9 @@ enum { V_SKINNY1 = 0, V_SKINNY9, V_SKINNY9S, V_128x64, V_64x64, V_64x128, V_128x
 
 // The variant table, in the order of the enum (tests/test_abi.py pins names and order).  4-wave tiles: 256 threads, a ring of ST
 // stages of (BM + BN) rows of 128 B - at most 72 KB per block, so two blocks (8 waves) share a CU's 160 KB LDS and hide each
-// other's barriers / epilogues.
+// other's barriers / epilogues.  ST_<tile>: the tile's LDS-DMA ring depth (K-steps in flight = depth - 1; the A/B of the depths is
+// profiles/r02_ab_experiments.md).
+constexpr int ST_128x64 = 3, ST_64x64 = 3, ST_64x128 = 3, ST_128x128 = 2;
 #define CRIS_TILE4_KERNS(K, BM, BN, WM, WN, ST) K<BM, BN, WM, WN, ST, 0>, K<BM, BN, WM, WN, ST, 1>, K<BM, BN, WM, WN, ST, 2>
 #define CRIS_TILE4_ROW(NAME, BM, BN, WM, WN, ST)                                                                           \
     {NAME, BM, BN, 256, ST * (BM + BN) * 128, BM / WM, 8,                                                                  \
@@ -650,56 +586,49 @@ static int pick_variant(const cris_conv_gemm_params& p) {
     // 8-wave ping-pong tiles (gemm8.hip; one block per CU): chosen from the per-shape A/B of tools/gemm_variants.py
     // (profiles/r03_gemm_variants.tsv).  CRIS_GEMM8=0 switches the family off.
     static const int g8 = cris_env_int("CRIS_GEMM8", 1);
-    static const int g8_min = cris_env_int("CRIS_GEMM8_MIN_TILES", 150);
-    static const int g8_min_k = cris_env_int("CRIS_GEMM8_MIN_K", 256);
+    constexpr int GEMM8_MIN_TILES = 150;            // fewest 256x256 / 128x256 tiles that take those tiles
+    constexpr int GEMM8_MIN_K = 256;
     // (upper bound 200 -> 216 in round 5: takes in the M 5408 / N 514 / K 4608 CoordConv layer, 43 x 5 tiles - 37.4 against 47.3 us
     // standalone, 12.012 / 12.003 against 12.061 / 12.026 ms per step, call r05j)
-    static const int g8_t128_lo = cris_env_int("CRIS_GEMM8_T128_LO", 100), g8_t128_hi = cris_env_int("CRIS_GEMM8_T128_HI", 216);
+    constexpr int GEMM8_T128_LO = 100, GEMM8_T128_HI = 216;        // 128x128 tiles of a problem that takes the 8-wave 128x128 tile
     // (lean epilogues only: the general epilogue on a 64x32 .. 128x64 wave tile spills and runs 1.3 - 1.6x longer than on the
     // 4-wave tiles - 25.8 against 15.8 us for the decoder's M 5408 / N 512 / K 512 projections, in-step kernel trace of call r03f)
     if (g8 && epilogue_kind(p) != 0 && (p.C & 63) == 0 && p.N >= 128) {
         const long t128 = (long)cris_cdiv(p.M, 128) * cris_cdiv(p.N, 128);
         // 128x128 with a five-deep ring: problems of 0.4 - 0.8 tiles per CU whose loop is bound by operand latency (mid-size
         // layers: M 5408 x N 512, M 1352 x N 2048, M 21632 x N 128): 36 against 51 us at M 5408 / N 512 / K 4608
-        if (p.K >= 512 && t128 >= g8_t128_lo && t128 <= g8_t128_hi) return V_8W_128x128;
-        if (p.N > 128 && p.K >= g8_min_k) {
+        if (p.K >= 512 && t128 >= GEMM8_T128_LO && t128 <= GEMM8_T128_HI) return V_8W_128x128;
+        if (p.N > 128 && p.K >= GEMM8_MIN_K) {
             const long t256 = (long)cris_cdiv(p.M, 256) * cris_cdiv(p.N, 256);
             // (a grid of 1.0 .. 1.5 waves of 256x256 tiles idles half the chip in its second round: halve the rows instead;
             // with K = 256 the 128x128 tile is level or ahead except where the 128x256 tiles fit in one round)
-            if (p.K >= 512 && t256 >= g8_min && !(t256 > 256 && t256 <= 400)) return V_8W_256x256;
+            if (p.K >= 512 && t256 >= GEMM8_MIN_TILES && !(t256 > 256 && t256 <= 400)) return V_8W_256x256;
             const long t128x256 = (long)cris_cdiv(p.M, 128) * cris_cdiv(p.N, 256);
-            if (t128x256 >= g8_min && !(t128x256 > 256 && t128x256 <= 400) && (p.K >= 512 || t128x256 <= 256)) return V_8W_128x256;
+            if (t128x256 >= GEMM8_MIN_TILES && !(t128x256 > 256 && t128x256 <= 400) && (p.K >= 512 || t128x256 <= 256)) return V_8W_128x256;
         }
     }
     // (Measured and rejected, call r03e: the 64x64 / 64x128 tiles with an 8- / 6-deep ring and one block per CU for the M 1352
     // layers - 30.1 against 29.3 us at M 1352 / N 512 / K 4608, the wider one 41 against 29: those layers are not short of
     // operands in flight.)
     // N <= 64: the 64x64 tile beats 128x64 on every such layer of the step (per-shape A/B: 20.8 against 23.8 us at M 86528 /
-    // N 64 / K 576, 47.8 against 49.3 at M 346112 / N 32 / K 288); CRIS_GEMM_NARROW_128=1 brings the 128x64 tile back
-    static const int narrow128 = cris_env_int("CRIS_GEMM_NARROW_128", 0);
-    if (p.N <= 64) return narrow128 ? V_128x64 : V_64x64;
+    // N 64 / K 576, 47.8 against 49.3 at M 346112 / N 32 / K 288)
+    if (p.N <= 64) return V_64x64;
     // too few 128x128 tiles to occupy the chip: halve the tile (2 blocks of 72 KB LDS fit a CU).  Mid-size problems
     // (M <= 8192 rows: layers 3-4, neck, decoder) never take the 128x128 tile even when N is wide: measured on the decoder FFN
     // (M 5408, N 2048, K 512) 37 us with 64-row tiles against 48 us.
-    static const int t128_min = cris_env_int("CRIS_GEMM_T128_MIN", 448);
-    if (p.M <= 8192 || (long)cris_cdiv(p.M, 128) * cris_cdiv(p.N, 128) < t128_min) {
+    constexpr int GEMM_T128_MIN = 448;
+    if (p.M <= 8192 || (long)cris_cdiv(p.M, 128) * cris_cdiv(p.N, 128) < GEMM_T128_MIN) {
         // latency-bound mid-size problems: more, smaller blocks (3 per CU at 48 KB LDS) hide each other's pipeline fill,
         // barriers and epilogues - except for long reductions (K >= 4096) over enough rows, where the 64x64 tile's LDS read
         // traffic (two fragment loads per MFMA) is the limit and the 64x128 tile (1.5 per MFMA) wins (measured: M 5408, N 512,
         // K 9216: 96 us against 119 us; K 4608: 54 against 57)
-        static const int t64_max = cris_env_int("CRIS_GEMM_T64_MAX", 1024);
+        constexpr int GEMM_T64_MAX = 1024;
         const bool long_k = p.K >= 4096 && p.M >= 4096 && p.N >= 256;
-        if (!long_k && (long)cris_cdiv(p.M, 64) * cris_cdiv(p.N, 128) < t64_max) {
-            // grids of at most two blocks per CU: the K-steps split over two wave groups inside the block (CRIS_GEMM_KS2=1; K >= 256
-            // so that each group has at least two steps).  Measured, call r03af: 12.27 ms per step (grids <= 512 blocks) and 12.20
-            // (<= 256) against 12.17 without - twice the waves do not pay for the two-deep rings and the combine; stays off,
-            // available by name ("64x64k2")
-            static const int ks2 = cris_env_int("CRIS_GEMM_KS2", 0), ks2_max = cris_env_int("CRIS_GEMM_KS2_MAX_BLOCKS", 512);
-            static const int ks2_min_k = cris_env_int("CRIS_GEMM_KS2_MIN_K", 256);
-            // (the K-split tile has no BatchNorm-backward epilogue: EPI 3 problems keep the plain 64x64 tile)
-            if (ks2 && p.K >= ks2_min_k && epilogue_kind(p) != 3 && (long)cris_cdiv(p.M, 64) * cris_cdiv(p.N, 64) <= ks2_max) return V_64x64_K2;
-            return V_64x64;
-        }
+        // (Grids of at most two blocks per CU with the K-steps split over two wave groups inside the block, "64x64k2", for K >= 256
+        // so that each group has at least two steps: measured, call r03af: 12.27 ms per step (grids <= 512 blocks) and 12.20
+        // (<= 256) against 12.17 without - twice the waves do not pay for the two-deep rings and the combine; never chosen here,
+        // available by name.  It has no BatchNorm-backward epilogue.)
+        if (!long_k && (long)cris_cdiv(p.M, 64) * cris_cdiv(p.N, 128) < GEMM_T64_MAX) return V_64x64;
         return V_64x128;
     }
     return V_128x128;

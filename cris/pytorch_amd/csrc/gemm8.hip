@@ -6,15 +6,16 @@
 // fragments.  Here a block is 512 threads = 8 waves = TWO wave groups of four (wave w and w+4 share a SIMD) on a 256x256,
 // 256x128 or 128x256 tile (one block per CU, 128-144 KB of LDS):
 //   * each group owns half of the tile's rows; a K-tile (64 deep) is worked off in phases of 8 v_mfma_f32_32x32x16_bf16
-//     (a 64x32 sub-block of the wave tile x K 64); a phase = MEM segment {issue the LDS-DMAs of one staging piece, read
-//     this phase's fragments from LDS, counted wait} - s_barrier - MFMA segment {8 MFMAs at raised priority} - s_barrier;
+//     (a 64x32 sub-block of the wave tile x K 64); a phase = MEM segment {read this phase's fragments from LDS, counted
+//     wait} - s_barrier - MFMA segment {8 MFMAs at raised priority, the LDS-DMAs of one staging piece issued after the
+//     first two} - s_barrier (the 256x256 tile: 16 MFMAs, its DMAs issued at the head of the MEM segment);
 //   * group 1 runs ONE barrier behind group 0, so on every SIMD one wave is in its MFMA segment while its partner is in
 //     its MEM segment: the matrix pipe always has an owner and the fragment reads / DMA issue of one wave hide under the
 //     MFMAs of the other (MI355X_MICROARCH.md "Two waves per SIMD": alternate matrix-heavy with memory segments);
 //   * operands travel HBM/L2 -> LDS by LDS-DMA exactly as in gemm.hip (im2col gather and zero fill as per-lane SOURCE
 //     offsets through a raw buffer descriptor, lane-linear LDS image, XOR swizzle on the source side), but in PIECES of
 //     128 tile rows (the rows the next phases need first), issued 3-4 phases ahead of their first read; waits are counted
-//     (s_waitcnt vmcnt(6) / (8): three or four pieces stay in flight across the barriers), never a drain in the loop.
+//     (s_waitcnt vmcnt(4) / (8) / (12): two to six pieces stay in flight across the barriers), never a drain in the loop.
 // Hazards, by construction (ticks = barrier intervals; group 0 runs MEM_p at tick 2p, group 1 at tick 2p+1):
 //   RAW  a piece read in phase p is waited for (own vmcnt) at the END of MEM_{p-1} by every wave: both groups have passed
 //        that wait before the barrier in front of group 0's MEM_p;
@@ -23,36 +24,13 @@
 // Only convolutions with C % 64 == 0 (a 64-wide K-tile lies in one tap; every large layer of the networks) come here.
 #include "gemm_common.h"
 
-// Diagnostic build switch of tools/probe/gemm8_probe.hip (ablations: which unit bounds the loop).  0 in the library: every
-// `if constexpr` below folds away.  bit 0: no fragment reads in the loop; 1: no DMA issue in the loop; 2: no MFMAs;
-// 3: no barriers in the loop; 4: lgkmcnt(0) after the barrier instead of before; 5: no s_setprio; 6: no group stagger;
-// 7 (results stay correct): flips where a phase's DMAs are issued - in front of the fragment reads (default of the 256x256
-// tile) or inside the MFMA segment after the first MFMAs (default of the 256x128 / 128x256 tiles; each default measured).
-#ifndef G8_ABL
-#define G8_ABL 0
-#endif
-
+// vmcnt(N) and lgkmcnt(0) in one s_waitcnt: at most N LDS-DMAs stay in flight, every LDS read of this wave is complete
 #define CRIS_WAIT_VM_LGKM0(N) __builtin_amdgcn_s_waitcnt(((N) & 0xF) | ((((N) >> 4) & 3) << 14) | (0x7 << 4))
-#define CRIS_WAIT_LGKM0() __builtin_amdgcn_s_waitcnt(0xF | (3 << 14) | (0x7 << 4))
 #define CRIS_BARRIER()                              \
     do {                                            \
         __builtin_amdgcn_sched_barrier(0);          \
         __builtin_amdgcn_s_barrier();               \
         __builtin_amdgcn_sched_barrier(0);          \
-    } while (0)
-// barrier / waits of the main loop (the ablation switches act on these only)
-#define LOOP_BARRIER()                              \
-    do {                                            \
-        if constexpr (!(G8_ABL & 8)) CRIS_BARRIER(); \
-        else __builtin_amdgcn_sched_barrier(0);     \
-    } while (0)
-/* N: DMAs that may stay in flight at the wait; N7: the same when the phase's own pieces are issued later (bit 7) */
-#define G8_VM(N, N7) (DMA_IN_MFMA ? (N7) : (N))
-#define LOOP_WAIT(N, N7)                                                                      \
-    do {                                                                                  \
-        if constexpr (G8_ABL & 2) { if constexpr (!(G8_ABL & 16)) CRIS_WAIT_LGKM0(); }    \
-        else if constexpr (G8_ABL & 16) CRIS_VMCNT(G8_VM(N, N7));                             \
-        else CRIS_WAIT_VM_LGKM0(G8_VM(N, N7));                                                \
     } while (0)
 
 // PA x PB sub-blocks of 64 x 32 per wave tile; wave grid 2 (M) x 4 (N):
@@ -71,7 +49,9 @@ __device__ __forceinline__ void conv_gemm8_tile(const cris_conv_gemm_params& p, 
     constexpr bool S4 = PA == 2 && PB == 2;
     constexpr bool S1 = PA == 1 && PB == 1;
     constexpr int NBUF = gemm8_nbuf(PA, PB);
-    constexpr bool DMA_IN_MFMA = (!S4) != ((G8_ABL & 128) != 0);      // where a phase issues its LDS-DMAs (see G8_ABL bit 7)
+    // a phase issues its LDS-DMAs inside the MFMA segment, after the first MFMAs; the 256x256 tile issues them in front of
+    // its fragment reads (the opposite placement was measured on each tile and rejected, profiles/r03_gemm8_probe.md)
+    constexpr bool DMA_IN_MFMA = !S4;
     constexpr int A_BYTES = BM * 128, TILE_BYTES = (BM + BN) * 128;
 
     const int t = threadIdx.x;
@@ -87,10 +67,7 @@ __device__ __forceinline__ void conv_gemm8_tile(const cris_conv_gemm_params& p, 
     // 191 against 198 us at M 86528 / N 512 / K 2304; the 128x128 tile keeps a weight panel (35.5 against 39.8 us at
     // M 5408 / N 512 / K 4608); the two 2-phase tiles follow gemm.hip's rule (weights beyond 2 MB: m fastest)
     int tile_m, tile_n;
-#ifndef G8_ORDER
-#define G8_ORDER 0                                  // probe: 1 = n fastest always, 2 = m fastest always
-#endif
-    const bool m_fastest = G8_ORDER == 2 || (G8_ORDER == 0 && (S1 || (!S4 && (long)p.N * p.K > (1L << 20))));
+    const bool m_fastest = S1 || (!S4 && (long)p.N * p.K > (1L << 20));
     if (m_fastest) {
         tile_n = cris_fast_div(bid, tiles_m, __builtin_amdgcn_rcpf((float)tiles_m));
         tile_m = bid - tile_n * tiles_m;
@@ -221,75 +198,61 @@ __device__ __forceinline__ void conv_gemm8_tile(const cris_conv_gemm_params& p, 
     // asm statements pin the MFMAs to their segment: an MFMA is a pure register operation, and without them hipcc sinks the
     // MFMAs of one phase across the barriers into the next phase's segment (seen in the disassembly) - which would put the
     // two wave groups' matrix work back to back on the same SIMD instead of alternating it with their memory segments.
-#define CRIS_MFMA_SEG(a, b, ISSUE)                                                                                           \
+#define CRIS_MFMA_SEG(a, b, ISSUE)                                                                                      \
     do {                                                                                                                \
-        if constexpr ((G8_ABL & 16) != 0) CRIS_WAIT_LGKM0();                                                            \
         asm volatile("" : "+v"(acc[(a) * 2 + 0][b]), "+v"(acc[(a) * 2 + 1][b]));                                        \
-        if constexpr (!(G8_ABL & 32)) __builtin_amdgcn_s_setprio(1);                                                    \
-        if constexpr (!(G8_ABL & 4)) _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                 \
+        __builtin_amdgcn_s_setprio(1);                                                                                  \
+        _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                              \
             acc[(a) * 2 + 0][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][ks], bfr[b][ks], acc[(a) * 2 + 0][b], 0, 0, 0); \
             acc[(a) * 2 + 1][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][ks], bfr[b][ks], acc[(a) * 2 + 1][b], 0, 0, 0); \
             if (ks == 0) { ISSUE; }                                                                                     \
         }                                                                                                               \
         asm volatile("" : "+v"(acc[(a) * 2 + 0][b]), "+v"(acc[(a) * 2 + 1][b]));                                        \
-        if constexpr (!(G8_ABL & 32)) __builtin_amdgcn_s_setprio(0);                                                                                  \
+        __builtin_amdgcn_s_setprio(0);                                                                                  \
     } while (0)
 
     // a 64-row half of the wave tile x both 32-column halves x K 64: 16 MFMAs on four accumulators (256x256 tile)
-#define CRIS_MFMA_SEG16(a, ISSUE)                                                                                       \
+#define CRIS_MFMA_SEG16(a)                                                                                              \
     do {                                                                                                                \
-        if constexpr ((G8_ABL & 16) != 0) CRIS_WAIT_LGKM0();                                                            \
         asm volatile("" : "+v"(acc[(a) * 2][0]), "+v"(acc[(a) * 2 + 1][0]), "+v"(acc[(a) * 2][1]), "+v"(acc[(a) * 2 + 1][1])); \
-        if constexpr (!(G8_ABL & 32)) __builtin_amdgcn_s_setprio(1);                                                    \
-        if constexpr (!(G8_ABL & 4)) _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                 \
+        __builtin_amdgcn_s_setprio(1);                                                                                  \
+        _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                              \
             _Pragma("unroll") for (int b = 0; b < 2; ++b) {                                                             \
                 acc[(a) * 2 + 0][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][ks], bfr[b][ks], acc[(a) * 2 + 0][b], 0, 0, 0); \
                 acc[(a) * 2 + 1][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][ks], bfr[b][ks], acc[(a) * 2 + 1][b], 0, 0, 0); \
             }                                                                                                           \
-            if (ks == 0) { ISSUE; }                                                                                     \
         }                                                                                                               \
         asm volatile("" : "+v"(acc[(a) * 2][0]), "+v"(acc[(a) * 2 + 1][0]), "+v"(acc[(a) * 2][1]), "+v"(acc[(a) * 2 + 1][1])); \
-        if constexpr (!(G8_ABL & 32)) __builtin_amdgcn_s_setprio(0);                                                    \
+        __builtin_amdgcn_s_setprio(0);                                                                                  \
     } while (0)
 
-#define LI_A(a) do { if constexpr (!(G8_ABL & 2) && !DMA_IN_MFMA) issue_A(a); } while (0)
-#define LI_B(b) do { if constexpr (!(G8_ABL & 2) && !DMA_IN_MFMA) issue_B(b); } while (0)
-#define MI_A(a) do { if constexpr (!(G8_ABL & 2) && DMA_IN_MFMA) issue_A(a); } while (0)
-#define MI_B(b) do { if constexpr (!(G8_ABL & 2) && DMA_IN_MFMA) issue_B(b); } while (0)
-#define LR_A(a) do { if constexpr (!(G8_ABL & 1)) read_A(a); } while (0)
-#define LR_B(b) do { if constexpr (!(G8_ABL & 1)) read_B(b); } while (0)
     const int nk = p.K / BK;
-    if constexpr ((G8_ABL & 1) != 0) {
-        read_A(0);
-#pragma unroll
-        for (int b = 0; b < PB; ++b) read_B(b);
-    }
-    if constexpr (S4) {
+    if constexpr (!DMA_IN_MFMA) {
         // 256x256: two phases of 16 MFMAs per K-tile.  Piece stream: A0 B0 B1 A1 | A0 B0 B1 A1 ...; phase 1 of K-tile t issues
         // A1(t+1), phase 2 issues A0(t+2) B0(t+2) B1(t+2) (every piece as early as its ring slot allows: two phases ahead)
         issue_A(0); issue_B(0); issue_B(1); issue_A(1); issue_A(0); issue_B(0); issue_B(1);
         CRIS_WAIT_VM_LGKM0(8);                      // A0(0), B0(0), B1(0) of this wave have landed
         CRIS_BARRIER();
-        if ((G8_ABL & 64) == 0 && wm == 1) CRIS_BARRIER();                // group 1 runs one barrier behind from here on
+        if (wm == 1) CRIS_BARRIER();                // group 1 runs one barrier behind from here on
         for (int kt = 0; kt < nk; ++kt) {
             // phase 1: rows 0..63 of the wave tile
-            LI_A(1);
-            LR_A(0);
-            LR_B(0);
-            LR_B(1);
-            LOOP_WAIT(8, 6);               // fragments in registers; A1(kt) landed (4 pieces stay in flight)
-            LOOP_BARRIER();
-            CRIS_MFMA_SEG16(0, MI_A(1));
-            LOOP_BARRIER();
+            issue_A(1);
+            read_A(0);
+            read_B(0);
+            read_B(1);
+            CRIS_WAIT_VM_LGKM0(8);                  // fragments in registers; A1(kt) landed (4 pieces stay in flight)
+            CRIS_BARRIER();
+            CRIS_MFMA_SEG16(0);
+            CRIS_BARRIER();
             // phase 2: rows 64..127
-            LI_A(0);
-            LI_B(0);
-            LI_B(1);
-            LR_A(1);
-            LOOP_WAIT(8, 2);               // A0(kt+1), B0(kt+1), B1(kt+1) landed
-            LOOP_BARRIER();
-            CRIS_MFMA_SEG16(1, MI_A(0); MI_B(0); MI_B(1));
-            LOOP_BARRIER();
+            issue_A(0);
+            issue_B(0);
+            issue_B(1);
+            read_A(1);
+            CRIS_WAIT_VM_LGKM0(8);                  // A0(kt+1), B0(kt+1), B1(kt+1) landed
+            CRIS_BARRIER();
+            CRIS_MFMA_SEG16(1);
+            CRIS_BARRIER();
             rbuf = rbuf == 0 ? TILE_BYTES : 0;
         }
     } else if constexpr (S1) {
@@ -299,16 +262,14 @@ __device__ __forceinline__ void conv_gemm8_tile(const cris_conv_gemm_params& p, 
         for (int d = 0; d < D; ++d) { issue_A(0); issue_B(0); }
         CRIS_WAIT_VM_LGKM0((D - 1) * 4);            // K-tile 0 of this wave has landed
         CRIS_BARRIER();
-        if ((G8_ABL & 64) == 0 && wm == 1) CRIS_BARRIER();
+        if (wm == 1) CRIS_BARRIER();
         for (int kt = 0; kt < nk; ++kt) {
-            LI_A(0);
-            LI_B(0);
-            LR_A(0);
-            LR_B(0);
-            LOOP_WAIT((D - 1) * 4, (D - 2) * 4);     // K-tile kt+1 landed
-            LOOP_BARRIER();
-            CRIS_MFMA_SEG(0, 0, MI_A(0); MI_B(0));
-            LOOP_BARRIER();
+            read_A(0);
+            read_B(0);
+            CRIS_WAIT_VM_LGKM0((D - 2) * 4);        // K-tile kt+1 landed
+            CRIS_BARRIER();
+            CRIS_MFMA_SEG(0, 0, issue_A(0); issue_B(0));
+            CRIS_BARRIER();
             rbuf += TILE_BYTES;
             if (rbuf == NBUF * TILE_BYTES) rbuf = 0;
         }
@@ -317,22 +278,19 @@ __device__ __forceinline__ void conv_gemm8_tile(const cris_conv_gemm_params& p, 
         issue_A(0); issue_B(0); issue_A(1); issue_A(0); issue_B(0);
         CRIS_WAIT_VM_LGKM0(6);
         CRIS_BARRIER();
-        if ((G8_ABL & 64) == 0 && wm == 1) CRIS_BARRIER();
+        if (wm == 1) CRIS_BARRIER();
         for (int kt = 0; kt < nk; ++kt) {
-            LI_A(1);
-            LI_A(0);
-            LR_A(0);
-            LR_B(0);
-            LOOP_WAIT(8, 4);                  // A1(kt) landed (4 pieces stay in flight)
-            LOOP_BARRIER();
-            CRIS_MFMA_SEG(0, 0, MI_A(1); MI_A(0));
-            LOOP_BARRIER();
-            LI_B(0);
-            LR_A(1);
-            LOOP_WAIT(6, 4);                  // A0(kt+1), B(kt+1) landed
-            LOOP_BARRIER();
-            CRIS_MFMA_SEG(1, 0, MI_B(0));
-            LOOP_BARRIER();
+            read_A(0);
+            read_B(0);
+            CRIS_WAIT_VM_LGKM0(4);                  // A1(kt) landed
+            CRIS_BARRIER();
+            CRIS_MFMA_SEG(0, 0, issue_A(1); issue_A(0));
+            CRIS_BARRIER();
+            read_A(1);
+            CRIS_WAIT_VM_LGKM0(4);                  // A0(kt+1), B(kt+1) landed
+            CRIS_BARRIER();
+            CRIS_MFMA_SEG(1, 0, issue_B(0));
+            CRIS_BARRIER();
             rbuf += TILE_BYTES;
             if (rbuf == NBUF * TILE_BYTES) rbuf = 0;
         }
@@ -341,36 +299,27 @@ __device__ __forceinline__ void conv_gemm8_tile(const cris_conv_gemm_params& p, 
         issue_B(0); issue_A(0); issue_B(1); issue_B(0); issue_A(0);
         CRIS_WAIT_VM_LGKM0(6);
         CRIS_BARRIER();
-        if ((G8_ABL & 64) == 0 && wm == 1) CRIS_BARRIER();
+        if (wm == 1) CRIS_BARRIER();
         for (int kt = 0; kt < nk; ++kt) {
-            LI_B(1);
-            LI_B(0);
-            LR_A(0);
-            LR_B(0);
-            LOOP_WAIT(8, 4);
-            LOOP_BARRIER();
-            CRIS_MFMA_SEG(0, 0, MI_B(1); MI_B(0));
-            LOOP_BARRIER();
-            LI_A(0);
-            LR_B(1);
-            LOOP_WAIT(6, 4);
-            LOOP_BARRIER();
-            CRIS_MFMA_SEG(0, 1, MI_A(0));
-            LOOP_BARRIER();
+            read_A(0);
+            read_B(0);
+            CRIS_WAIT_VM_LGKM0(4);
+            CRIS_BARRIER();
+            CRIS_MFMA_SEG(0, 0, issue_B(1); issue_B(0));
+            CRIS_BARRIER();
+            read_B(1);
+            CRIS_WAIT_VM_LGKM0(4);
+            CRIS_BARRIER();
+            CRIS_MFMA_SEG(0, 1, issue_A(0));
+            CRIS_BARRIER();
             rbuf += TILE_BYTES;
             if (rbuf == NBUF * TILE_BYTES) rbuf = 0;
         }
     }
-    if ((G8_ABL & 64) == 0 && wm == 0) CRIS_BARRIER();    // same number of barriers for every wave
+    if (wm == 0) CRIS_BARRIER();                    // same number of barriers for every wave
     CRIS_VMCNT(0);                                  // drain the (out-of-range) tail DMAs before the block retires
 #undef CRIS_MFMA_SEG
 #undef CRIS_MFMA_SEG16
-#undef LI_A
-#undef MI_A
-#undef MI_B
-#undef LI_B
-#undef LR_A
-#undef LR_B
 
     // (An epilogue staged through LDS - DPP pair exchange, 16-byte row stores instead of 2-byte stores in the C/D layout - was
     // measured on the probe: no difference, 193.8 against 194.8 us at M 86528 / N 512 / K 2304; the fixed ~16 us per 256x256

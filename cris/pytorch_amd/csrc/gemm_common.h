@@ -8,12 +8,6 @@
 #include <type_traits>
 
 #define BK 64
-#ifndef CRIS_FAST_EPILOGUE
-#define CRIS_FAST_EPILOGUE 1      // 0: always the general epilogue (A/B builds)
-#endif
-#ifndef CRIS_FAST_EPILOGUE_GEN
-#define CRIS_FAST_EPILOGUE_GEN 1  // 0: EPI 0 always takes the general form (A/B builds)
-#endif
 
 // XCD-aware block order: blocks b, b+8, b+16 .. run on the same XCD (round-robin dispatch); XCD x gets the CONTIGUOUS run of
 // logical blocks [x*total/8, (x+1)*total/8) so that its private L2 keeps the operand panel the run shares
@@ -106,7 +100,7 @@ __device__ __forceinline__ void gemm_epilogue_fast32(const cris_conv_gemm_params
                 acc[i][j][e] = x;
                 s1 += x;
                 const bf16_t xb = f2bf_hw(x);
-                __builtin_amdgcn_raw_buffer_store_b16((short)xb, rsO, vo[e & 3], so, CRIS_STORE_AUX);
+                __builtin_amdgcn_raw_buffer_store_b16((short)xb, rsO, vo[e & 3], so, 0);
                 if (bnr) {                          // as bn_bwd_reduce_kernel (MASK 2) on the STORED gradient
                     const float g = (yv[e] * b_sc + b_sh) > 0.f ? bf2f(xb) : 0.f;
                     b0 += g;
@@ -209,8 +203,8 @@ __device__ __forceinline__ void gemm_epilogue_fast32_gen(const cris_conv_gemm_pa
                 if (act == 3) x = fmaxf(x, 0.f);
                 acc[i][j][e] = x;
                 s1 += x;
-                if constexpr (OUT_F32) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), rsO, vo[e & 3], so, CRIS_STORE_AUX);
-                else __builtin_amdgcn_raw_buffer_store_b16((short)f2bf_hw(x), rsO, vo[e & 3], so, CRIS_STORE_AUX);
+                if constexpr (OUT_F32) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), rsO, vo[e & 3], so, 0);
+                else __builtin_amdgcn_raw_buffer_store_b16((short)f2bf_hw(x), rsO, vo[e & 3], so, 0);
             }
             if (has_T) {
 #pragma unroll
@@ -273,14 +267,14 @@ __device__ __forceinline__ void gemm_epilogue(const cris_conv_gemm_params& p, AC
     // both: per lane NG groups of 4 consecutive rows of one column
     if constexpr (EPI != 0 && MT == 32 && std::is_same<ACC, f32x16>::value) {
         // wave-uniform: the whole wave tile lies inside the problem -> the cheap form (same values)
-        if (p.out && row0 + FM * 32 <= p.M && col0 + FN * 32 <= p.N && CRIS_FAST_EPILOGUE) {
+        if (p.out && row0 + FM * 32 <= p.M && col0 + FN * 32 <= p.N) {
             gemm_epilogue_fast32<EPI, FM, FN>(p, acc, row0, col0, part, lane);
             return;
         }
     }
     if constexpr (EPI == 0 && MT == 32 && std::is_same<ACC, f32x16>::value) {
         // interior wave tile, no dropout: the cheap general form (bias / activation / fp32 streams / transposed copy)
-        if (CRIS_FAST_EPILOGUE_GEN && row0 + FM * 32 <= p.M && col0 + FN * 32 <= p.N && p.drop_thresh == 0u && (!p.outT || p.T_L >= 8)) {
+        if (row0 + FM * 32 <= p.M && col0 + FN * 32 <= p.N && p.drop_thresh == 0u && (!p.outT || p.T_L >= 8)) {
             const bool rf = p.resid && p.resid_f32, of = p.out && p.out_f32;
             if (!rf && !of) { gemm_epilogue_fast32_gen<false, false, FM, FN>(p, acc, row0, col0, part, lane); return; }
             if (rf && of) { gemm_epilogue_fast32_gen<true, true, FM, FN>(p, acc, row0, col0, part, lane); return; }
@@ -343,8 +337,8 @@ __device__ __forceinline__ void gemm_epilogue(const cris_conv_gemm_params& p, AC
                 vals[ig][r] = x;
                 if (has_out) {
                     const unsigned off = valid ? ((unsigned)m * (unsigned)p.ldc + (unsigned)(p.c_coff + col)) * out_es : CRIS_OOB;
-                    if (out_f32) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), rsO, off, 0, CRIS_STORE_AUX);
-                    else __builtin_amdgcn_raw_buffer_store_b16((short)f2bf(x), rsO, off, 0, CRIS_STORE_AUX);
+                    if (out_f32) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), rsO, off, 0, 0);
+                    else __builtin_amdgcn_raw_buffer_store_b16((short)f2bf(x), rsO, off, 0, 0);
                 }
             }
             if (!LEAN && p.outT && cvalid && rowb < p.M) {

@@ -15,12 +15,7 @@
 #include "gemm_common.h"
 
 #define BK8 128                 // fp8 K elements per K-step (one 128-B LDS row)
-#ifndef ST8_64x64
-#define ST8_64x64 3
-#endif
-#ifndef ST8_128x128
-#define ST8_128x128 2
-#endif
+constexpr int ST8_64x64 = 3, ST8_128x128 = 2;      // LDS-DMA ring depth per tile (as the bf16 tiles of gemm.hip)
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;      // 32 fp8 operand bytes of one lane (f8f6f4 MFMA, 32x32x64)
 
@@ -274,11 +269,11 @@ __global__ __launch_bounds__(256) void conv_gemm_fp8_kernel(const cris_conv_gemm
                 if (act == 3) x = fmaxf(x, 0.f);
                 if (has_out) {
                     const unsigned off = valid ? ((unsigned)m * (unsigned)p.ldc + (unsigned)(p.c_coff + col)) * 2u : CRIS_OOB;
-                    __builtin_amdgcn_raw_buffer_store_b16((short)f2bf_hw(x), rsO, off, 0, CRIS_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b16((short)f2bf_hw(x), rsO, off, 0, 0);
                 }
                 if (has_out8) {
                     const unsigned off = valid ? (unsigned)m * (unsigned)p.ldq + (unsigned)(p.q_coff + col) : CRIS_OOB;
-                    __builtin_amdgcn_raw_buffer_store_b8((char)cris_f32_to_e4m3(__builtin_amdgcn_ldexpf(x, -p.e_y)), rsQ, off, 0, CRIS_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b8((char)cris_f32_to_e4m3(__builtin_amdgcn_ldexpf(x, -p.e_y)), rsQ, off, 0, 0);
                 }
             }
         }

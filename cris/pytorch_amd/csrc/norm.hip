@@ -869,18 +869,18 @@ struct bn_bwd_geom {
     int chv, chunks, rpb, rbs;
 };
 static bn_bwd_geom bn_bwd_geometry(int M, int C) {
-    static const int max_blocks = cris_env_int("CRIS_BN_RED_BLOCKS", 512);
-    static const int min_rows = cris_env_int("CRIS_BN_RED_ROWS", 32);
+    constexpr int BN_RED_BLOCKS = 512;              // blocks a reduce launch aims for (chunks x row blocks)
+    constexpr int BN_RED_ROWS = 32;                 // fewest rows per row block
     bn_bwd_geom g;
     const int CV = C >> 3;
     g.chv = 1;
     while (g.chv < 8 && g.chv * 2 <= CV / 4) g.chv *= 2;       // ~C/4 channels per chunk, at most 64
     g.chunks = cris_cdiv(CV, g.chv);
-    int rbs = max_blocks / g.chunks;
+    int rbs = BN_RED_BLOCKS / g.chunks;
     if (rbs > 64) rbs = 64;
     if (rbs < 1) rbs = 1;
     g.rpb = cris_cdiv(M, rbs);
-    if (g.rpb < min_rows) g.rpb = min_rows;
+    if (g.rpb < BN_RED_ROWS) g.rpb = BN_RED_ROWS;
     g.rbs = cris_cdiv(M, g.rpb);
     return g;
 }
@@ -1338,10 +1338,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const cris_ln_bwd_params p)
     }
 }
 
-static int ln_bwd_grid(int rows) {
-    static const int max_grid = cris_env_int("CRIS_LN_BWD_BLOCKS", 512);
-    return cris_grid_1d(rows, 4, max_grid);
-}
+constexpr int LN_BWD_BLOCKS = 512;                  // largest grid (= rows of the partials table)
+static int ln_bwd_grid(int rows) { return cris_grid_1d(rows, 4, LN_BWD_BLOCKS); }
 extern "C" int cris_ln_bwd_parts(int rows) { return ln_bwd_grid(rows); }
 
 extern "C" int cris_ln_bwd(const cris_ln_bwd_params* pp, void* stream) {

@@ -1,7 +1,9 @@
 #!/bin/bash
-# A/B builds of libcris_hip.so: the same sources with extra -D switches, cross-compiled here (no GPU needed) into
+# A/B builds of libcris_hip.so: the same sources with extra compiler flags, cross-compiled here (no GPU needed) into
 # cris/pytorch_amd/csrc/variants/libcris_hip_<tag>.so (git-ignored, travels with gpurun); CRIS_LIB_VARIANT=<tag> loads one (hip.py).
-#   tools/build_variants.sh "sc1:-DCRIS_STORE_POLICY=1" "nt:-DCRIS_STORE_POLICY=2"
+#   tools/build_variants.sh "o2:-O2" "base:"
+# Run from a checkout of another commit it builds that commit's library the same way ("parent:"): copied into this tree's
+# variants/ it is the other side of an A/B of two commits whose Python side is the same (profiles/strip_scaffolding.md).
 set -e
 cd "$(dirname "$0")/../cris/pytorch_amd/csrc"
 mkdir -p variants
