@@ -336,6 +336,112 @@ __global__ __launch_bounds__(256) void predict_masks_batch_kernel(const float* _
     }
 }
 
+// ---- threshold sweep: warp + classification against T ascending thresholds + counts for n ragged descriptors in one launch ----
+// The grid, the 4-pixel groups, the mask dword and the per-pixel value are eval_iou_batch_kernel's.  Per pixel
+// k = #{i : value > thr[i]} (comparisons of exactly that form: a bracket test against thr[0] and thr[T-1], a binary search
+// between them; a NaN gives 0) and m = (mask byte != 0).  Column i of the table needs  pred_i = #(k > i),  inter_i = #(k > i, m)
+// and gt = #(m):  union_i = pred_i + gt - inter_i.  The bins with k = 0 enter no pred_i or inter_i, so they are never counted;
+// gt and the two k = T bins (confident foreground - with k = 0 the bulk of a bimodal map) stay in registers and go through the
+// wave shuffle; only 0 < k < T (pixels between the lowest and the highest threshold: the rim of a segment) go to the wave's LDS
+// histogram hist[wave][m][k - 1], equal keys of a thread's four pixels merged into one ds_add.  Block end: the four waves'
+// histograms are summed, thread i < T takes the suffix sums over k, one integer atomicAdd pair per (block, i) with a non-zero
+// term (exact, order-free: every run gives the same table).
+#define EP_SWEEP_MAX 64
+struct ep_thr_tab {
+    float v[EP_SWEEP_MAX];
+};
+
+__global__ __launch_bounds__(256) void eval_iou_sweep_batch_kernel(const float* __restrict__ probs, int H, int W,
+                                                                   const cris_eval_desc* __restrict__ descs,
+                                                                   const unsigned char* __restrict__ masks, const ep_cubic_tab t,
+                                                                   const ep_thr_tab th, int T, float border, int* __restrict__ counts) {
+    __shared__ float tab[32][4];
+    __shared__ float thr[EP_SWEEP_MAX];
+    __shared__ int hist[4][2][EP_SWEEP_MAX];                        // [wave][mask bit][k - 1], 0 < k < T
+    __shared__ int red[3][4];
+    if (threadIdx.x < 128) tab[threadIdx.x >> 2][threadIdx.x & 3] = t.tab[threadIdx.x >> 2][threadIdx.x & 3];
+    if (threadIdx.x < EP_SWEEP_MAX) thr[threadIdx.x] = th.v[threadIdx.x];
+    for (int i = threadIdx.x; i < 4 * 2 * EP_SWEEP_MAX; i += blockDim.x) (&hist[0][0][0])[i] = 0;
+    __syncthreads();
+    const cris_eval_desc d = descs[blockIdx.y];
+    const float* __restrict__ src = probs + (size_t)d.map * H * W;
+    const unsigned char* __restrict__ mrow = masks + d.mask_off;
+    const int gpr = d.pitch >> 2;                                  // groups per row (the pitch is a multiple of 4)
+    const long total = (long)gpr * d.h_out;
+    const float thr_lo = thr[0], thr_hi = thr[T - 1];
+    int (*const my)[EP_SWEEP_MAX] = hist[threadIdx.x >> 6];
+    int gt = 0, top = 0, top_m = 0;                                // #(m), #(k == T), #(k == T, m)
+    for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long)gridDim.x * blockDim.x) {
+        const int y = (int)(g / gpr), x0 = (int)(g % gpr) * 4;
+        const size_t boff = (size_t)y * d.pitch + x0;
+        const unsigned int mword = *reinterpret_cast<const unsigned int*>(mrow + boff);
+        long X0, Y0;
+        ep_warp_row(d.m, y, X0, Y0);
+        int run_key = -1, run = 0;                                 // the pending LDS add: key = m * EP_SWEEP_MAX + k - 1
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = x0 + j;
+            if (x < d.w_out) {                                     // (lanes past w_out: padding bytes, not counted)
+                const float acc = ep_warp_value(src, H, W, tab, d.m, X0, Y0, x, border);
+                const int m = ((mword >> (8 * j)) & 0xffu) != 0u ? 1 : 0;
+                gt += m;
+                if (acc > thr_lo) {                                // (false for a NaN: k = 0)
+                    if (acc > thr_hi) {
+                        top += 1;
+                        top_m += m;
+                    } else {                                       // 1 <= k <= T - 1: the first i with !(acc > thr[i])
+                        int lo = 1, hi = T - 1;
+                        while (lo < hi) {
+                            const int mid = (lo + hi) >> 1;
+                            if (acc > thr[mid]) lo = mid + 1; else hi = mid;
+                        }
+                        const int key = m * EP_SWEEP_MAX + lo - 1;
+                        if (key == run_key) {
+                            run += 1;
+                        } else {
+                            if (run) atomicAdd(&my[0][0] + run_key, run);
+                            run_key = key;
+                            run = 1;
+                        }
+                    }
+                }
+            }
+        }
+        if (run) atomicAdd(&my[0][0] + run_key, run);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        gt += __shfl_xor(gt, o, 64);
+        top += __shfl_xor(top, o, 64);
+        top_m += __shfl_xor(top_m, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = gt;
+        red[1][threadIdx.x >> 6] = top;
+        red[2][threadIdx.x >> 6] = top_m;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * EP_SWEEP_MAX) {                          // the four waves' histograms into wave 0's
+        const int b = threadIdx.x >> 6, k = threadIdx.x & 63;
+        hist[0][b][k] = hist[0][b][k] + hist[1][b][k] + hist[2][b][k] + hist[3][b][k];
+    }
+    __syncthreads();
+    if (threadIdx.x < T) {
+        const int i = threadIdx.x;
+        const int gts = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        int pred = red[1][0] + red[1][1] + red[1][2] + red[1][3];  // k == T
+        int inter = red[2][0] + red[2][1] + red[2][2] + red[2][3];
+        for (int k = i + 1; k < T; ++k) {                          // k > i, k < T
+            inter += hist[0][1][k - 1];
+            pred += hist[0][0][k - 1] + hist[0][1][k - 1];
+        }
+        int* row = counts + ((size_t)d.row * T + i) * 2;
+        const int uni = pred + gts - inter;
+        if (inter) atomicAdd(row, inter);
+        if (uni) atomicAdd(row + 1, uni);
+    }
+}
+
 extern "C" int cris_eval_desc_fill(cris_eval_desc* desc, const double* mat, int w_out, int h_out, int map, long mask_off, int pitch,
                                    long out_off, int row) {
     CRIS_CHECK_ARG(desc && mat, "bad args");
@@ -369,6 +475,41 @@ extern "C" int cris_eval_iou_batch(const float* probs, int P, int H, int W, cons
     const int cap = 2048 / n > 8 ? 2048 / n : 8;                   // ~2048 blocks in all, grid-stride for the rest
     hipLaunchKernelGGL(eval_iou_batch_kernel, dim3(cris_grid_1d(most, 256, cap), n), dim3(256), 0, (hipStream_t)stream, probs, H, W,
                        descs_dev, masks, t, thr, border, counts, out_masks);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cris_eval_iou_sweep_batch(const float* probs, int P, int H, int W, const cris_eval_desc* descs_host,
+                                         const cris_eval_desc* descs_dev, int n, const unsigned char* masks, size_t mask_bytes,
+                                         const float* thresholds, int T, float border, int* counts, int count_rows, void* stream) {
+    CRIS_CHECK_ARG(probs && descs_host && descs_dev && masks && thresholds && counts, "null operand");
+    CRIS_CHECK_ARG(P > 0 && H > 0 && W > 0 && count_rows > 0, "bad sizes");
+    CRIS_CHECK_ARG(n > 0 && n <= 65535, "n must be in 1 .. 65535");
+    CRIS_CHECK_ARG(T >= 1 && T <= EP_SWEEP_MAX, "T must be in 1 .. 64");
+    ep_thr_tab th;
+    for (int i = 0; i < EP_SWEEP_MAX; ++i) {
+        th.v[i] = i < T ? thresholds[i] : thresholds[T - 1];       // (the kernel reads the first T)
+        if (i >= T) continue;
+        CRIS_CHECK_ARG(th.v[i] >= -3.0e38f && th.v[i] <= 3.0e38f, "thresholds must be finite");       // (false for a NaN)
+        CRIS_CHECK_ARG(i == 0 || th.v[i] > th.v[i - 1], "thresholds must be strictly increasing");
+    }
+    CRIS_CHECK_ARG(((uintptr_t)masks & 3) == 0 && ((uintptr_t)counts & 3) == 0, "masks and counts must be 4-byte aligned");
+    long most = 0;
+    for (int i = 0; i < n; ++i) {                                  // every address the kernel forms is checked here, on the host copy
+        const cris_eval_desc& d = descs_host[i];
+        CRIS_CHECK_ARG(d.w_out > 0 && d.h_out > 0 && (long)d.w_out * d.h_out < (1L << 31), "descriptor: bad output size");
+        CRIS_CHECK_ARG(d.map >= 0 && d.map < P && d.row >= 0 && d.row < count_rows, "descriptor: map / row out of range");
+        CRIS_CHECK_ARG(d.pitch >= d.w_out && (d.pitch & 3) == 0 && d.pitch - d.w_out < (1 << 20), "descriptor: the pitch must be a multiple of 4, >= w_out");
+        CRIS_CHECK_ARG(d.mask_off >= 0 && (d.mask_off & 3) == 0 && (size_t)d.mask_off + (size_t)d.pitch * d.h_out <= mask_bytes,
+                       "descriptor: mask outside the buffer");
+        const long groups = (long)(d.pitch >> 2) * d.h_out;
+        if (groups > most) most = groups;
+    }
+    ep_cubic_tab t;
+    ep_warp_setup(nullptr, nullptr, t.tab);
+    const int cap = 2048 / n > 8 ? 2048 / n : 8;                   // the grid of cris_eval_iou_batch
+    hipLaunchKernelGGL(eval_iou_sweep_batch_kernel, dim3(cris_grid_1d(most, 256, cap), n), dim3(256), 0, (hipStream_t)stream, probs, H, W,
+                       descs_dev, masks, t, th, T, border, counts);
     CRIS_LAUNCH_CHECK();
     return 0;
 }

@@ -13,7 +13,9 @@ libcris_hip.so (csrc/evalpost.hip) and only the two integer counts per sample co
 form that evaluate.Evaluator drives: steps 3-4 for a whole ragged batch in ONE launch, uint8 masks and the descriptor table
 packed into one pinned buffer (`EvalStaging`), the warped map never written, counts accumulated in a table for the whole pass.
 `predict_batch` is the same launch without ground truth (predict.Predictor): no mask goes up (`EvalStaging.pack_sizes`), the
-binary masks come out at the original sizes and (area, score, bounding box) accumulate in an int64 table (`new_predict_stats`)."""
+binary masks come out at the original sizes and (area, score, bounding box) accumulate in an int64 table (`new_predict_stats`).
+`iou_sweep_batch` is `iou_batch` at up to 64 thresholds in one launch (evaluate.Evaluator.sweep): counts [R, T, 2], column i what
+`iou_batch` counts at thresholds[i]."""
 import ctypes as C
 
 import numpy as np
@@ -186,6 +188,34 @@ def iou_batch(probs, descs, masks_u8, counts, row0, thr=0.35, out_masks=None, bo
     hip.call("cris_eval_iou_batch", ptr(probs), P, H, W, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n, ptr(masks_u8),
              masks_u8.numel(), float(thr), float(border), counts.data_ptr() + 8 * int(row0), counts.shape[0] - int(row0),
              ptr(out_masks), 0 if out_masks is None else out_masks.numel(), _stream())
+
+
+SWEEP_MAX = 64          # thresholds of one sweep launch (EP_SWEEP_MAX of csrc/evalpost.hip)
+
+
+def iou_sweep_batch(probs, descs, masks_u8, counts, row0, thresholds, border=0.0):
+    """`iou_batch` at T thresholds in ONE launch (cris_eval_iou_sweep_batch): the per-pixel value of every descriptor is computed
+    once and counts[row0 + row, i] += (intersection, union) of (value > thresholds[i]) against the mask, for every i - column i is
+    exactly what `iou_batch(..., thr=float(np.float32(thresholds[i])))` adds.  probs, descs, masks_u8: as for `iou_batch`; counts:
+    [R, T, 2] cuda int32, zeroed by the caller once per pass; thresholds: 1 .. 64 finite, strictly increasing values (rounded to
+    float32 once, here on the host; the library checks them).  No masks are written."""
+    if probs.device.type != "cuda":
+        raise RuntimeError("evalpost runs on the GPU only (no CPU fallback)")
+    if probs.dim() != 3 or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise ValueError("iou_sweep_batch: probs must be contiguous fp32 [P, H, W]")
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).astype(np.float32))
+    if thr.ndim != 1 or not 1 <= thr.shape[0] <= SWEEP_MAX:
+        raise ValueError("iou_sweep_batch: thresholds must be a list of 1 .. %d values" % SWEEP_MAX)
+    T = int(thr.shape[0])
+    if (counts.dtype != torch.int32 or counts.dim() != 3 or counts.shape[1] != T or counts.shape[2] != 2 or not counts.is_contiguous()
+            or not 0 <= row0 < counts.shape[0]):
+        raise ValueError("iou_sweep_batch: counts must be contiguous int32 [R, T, 2] with T = len(thresholds) and row0 inside it")
+    if masks_u8.dtype != torch.uint8 or not masks_u8.is_contiguous():
+        raise ValueError("iou_sweep_batch: masks_u8 must be a contiguous uint8 buffer")
+    P, H, W = probs.shape
+    hip.call("cris_eval_iou_sweep_batch", ptr(probs), P, H, W, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n, ptr(masks_u8),
+             masks_u8.numel(), thr.ctypes.data_as(C.c_void_p), T, float(border), counts.data_ptr() + 8 * T * int(row0),
+             counts.shape[0] - int(row0), _stream())
 
 
 PREDICT_FIELDS = ("area", "score_q16", "x_min", "y_min", "x_end", "y_end")

@@ -10,6 +10,9 @@ Per batch: RecordPipeline (JPEG decode + letter-box on the GPU), the model, `eva
 sample's row of a device table.  The masks come from the records' own `mask` bytes (tools/folder2lmdb.py:49-50 stores the file
 `mask_dir` names), packed as uint8 next to the descriptors in a pinned buffer: one asynchronous copy per batch.  The table is
 read ONCE, after the last batch - no batch waits for the host (a `visualize` callback needs each batch's result and does wait).
+
+`Evaluator.sweep` is either pass at many thresholds at once (`evalpost.iou_sweep_batch`, a [n, T, 2] table): `sweep_metrics` turns
+the table into a `SweepResult` - IoU, overall IoU and Pr@X per threshold, the best threshold - whose column t equals the pass at thr=t.
 """
 import math
 
@@ -38,6 +41,67 @@ def metrics(counts):
     n = np.float32(per.shape[0])
     prec = {k: float(np.float32(int((per > t).sum())) / n) for k, t in zip(PR_KEYS, pr_thresholds())}
     return float(per.mean()), prec, per
+
+
+def overall_iou(counts):
+    """counts: [n, 2] integers -> sum(inter) / (sum(union) + 1e-6) in float64: the cumulative ('overall') IoU of the split, the
+    second figure RefCOCO papers report next to the mean of the per-sample IoUs"""
+    c = np.asarray(counts, dtype=np.float64).reshape(-1, 2)
+    if c.shape[0] == 0:
+        raise ValueError("overall_iou: no samples")
+    return float(c[:, 0].sum() / (c[:, 1].sum() + 1e-6))
+
+
+def sweep_thresholds():
+    """the default grid of a threshold sweep: the 19 float32 values 0.05, 0.10, ... 0.95 (0.35, the reference's cut, is one)"""
+    return np.array([i / 20 for i in range(1, 20)], dtype=np.float32)
+
+
+class SweepResult:
+    """What `sweep_metrics` returns: `thresholds` float32 [T]; `iou` [T] (mean of the per-sample IoUs), `overall_iou` [T] and
+    `prec[key]` [T] as float64 arrays, `per_sample` [n, T]; entry i of each is the figure at thresholds[i]."""
+
+    def __init__(self, thresholds, iou, overall, prec, per_sample):
+        self.thresholds, self.iou, self.overall_iou, self.prec, self.per_sample = thresholds, iou, overall, prec, per_sample
+
+    def _metric(self, metric):
+        if metric == "iou":
+            return self.iou
+        if metric == "overall_iou":
+            return self.overall_iou
+        if metric in self.prec:
+            return self.prec[metric]
+        raise ValueError("SweepResult: metric must be 'iou', 'overall_iou' or one of %s" % (PR_KEYS,))
+
+    def best(self, metric="iou"):
+        """(threshold, value) of the largest `metric`; the lowest threshold wins a tie"""
+        v = self._metric(metric)
+        i = int(np.argmax(v))                                      # (the first maximum; thresholds ascend)
+        return float(self.thresholds[i]), float(v[i])
+
+    def at(self, thr):
+        """(iou, prec) at the threshold whose float32 value is float32(thr) - what `validate` / `inference` return at that thr"""
+        hit = np.nonzero(self.thresholds == np.float32(thr))[0]
+        if hit.size == 0:
+            raise KeyError("SweepResult: %r is not one of the swept thresholds" % (thr,))
+        i = int(hit[0])
+        return float(self.iou[i]), {k: float(v[i]) for k, v in self.prec.items()}
+
+
+def sweep_metrics(counts, thresholds):
+    """counts: [n, T, 2] integers (intersection, union) per sample and threshold, thresholds: the T ascending values -> SweepResult.
+    Column i goes through `metrics` itself, so entry i of iou / prec / per_sample is what `metrics(counts[:, i])` returns."""
+    thr = np.asarray(thresholds, dtype=np.float64).astype(np.float32)
+    c = np.asarray(counts)
+    if thr.ndim != 1 or thr.shape[0] == 0 or not (np.isfinite(thr).all() and (np.diff(thr) > 0).all()):
+        raise ValueError("sweep_metrics: thresholds must be a non-empty, finite, strictly increasing list")
+    if c.ndim != 3 or c.shape[1] != thr.shape[0] or c.shape[2] != 2:
+        raise ValueError("sweep_metrics: counts must be [n, T, 2] with T = len(thresholds)")
+    if c.shape[0] == 0:
+        raise ValueError("sweep_metrics: no samples")
+    cols = [metrics(c[:, i]) for i in range(thr.shape[0])]
+    return SweepResult(thr, np.array([m[0] for m in cols], np.float64), np.array([overall_iou(c[:, i]) for i in range(thr.shape[0])], np.float64),
+                       {k: np.array([m[1][k] for m in cols], np.float64) for k in PR_KEYS}, np.stack([m[2] for m in cols], 1))
 
 
 def shard_indices(n, rank, world):
@@ -104,7 +168,7 @@ class Evaluator:
         self._segment = getattr(model, "segment", None) or getattr(model, "segment_expressions", None)
         self._ring = [evalpost.EvalStaging(self.device) for _ in range(self.RING)]
         self._turn = 0
-        self.per_sample = self.counts = None
+        self.per_sample = self.counts = self.sweep_counts = None
 
     def _staging(self):
         self._turn = (self._turn + 1) % self.RING
@@ -180,6 +244,69 @@ class Evaluator:
                 self._visualize(visualize, recs, sents, index, st, table[row0:row0 + K].cpu().numpy(), out.cpu().numpy())
             row0 += K
         return self._finish(table, total, None)
+
+    @torch.no_grad()
+    def sweep(self, records, thresholds=None, split="validate", indices=None, batch_size=32, images_per_batch=8, group=None):
+        """The split at every threshold of `thresholds` (default sweep_thresholds()) in ONE pass -> SweepResult: the batch loop,
+        padding, staging ring and model shapes of `validate` (split="validate": first sentences, batches of `batch_size`) or of
+        `inference` (split="inference": every sentence, `images_per_batch` images share a visual pass), with
+        `evalpost.iou_sweep_batch` in place of `iou_batch` - one model call and one sweep launch per batch, the [n, T, 2] table
+        read once at the end (kept in `sweep_counts`).  Column i equals the `counts` of a pass at thr = thresholds[i]; `self.thr`
+        plays no part."""
+        if split not in ("validate", "inference"):
+            raise ValueError("sweep: split must be 'validate' or 'inference'")
+        if self.pipe.mode != ("val" if split == "validate" else "test"):
+            raise ValueError("sweep(split=%r) needs a RecordPipeline in mode %r" % (split, "val" if split == "validate" else "test"))
+        thr = sweep_thresholds() if thresholds is None else np.asarray(thresholds, dtype=np.float64).astype(np.float32)
+        if thr.ndim != 1 or not 1 <= thr.shape[0] <= evalpost.SWEEP_MAX or not (np.isfinite(thr).all() and (np.diff(thr) > 0).all()):
+            raise ValueError("sweep: thresholds must be 1 .. %d finite, strictly increasing values" % evalpost.SWEEP_MAX)
+        indices = list(range(len(records))) if indices is None else [int(i) for i in indices]
+        if not indices:
+            raise ValueError("sweep: no records")
+        T = int(thr.shape[0])
+        if split == "validate":
+            total = len(indices)
+            table = torch.zeros(total, T, 2, dtype=torch.int32, device=self.device)
+            for lo in range(0, total, batch_size):
+                recs = [records[i] for i in indices[lo:lo + batch_size]]
+                img, word, params = self.pipe(recs)
+                n = len(recs)
+                if n < batch_size:                                 # short last batch: repeat its last sample, one graph shape
+                    rep = torch.tensor(list(range(n)) + [n - 1] * (batch_size - n), device=self.device)
+                    img, word = img[rep], word[rep]
+                st = self._staging().pack(*plan_validate(self._masks(recs, params), [p["inverse"] for p in params])).upload()
+                probs = evalpost.sigmoid_upsample(self.model(img, word), img.shape[-2], img.shape[-1])
+                evalpost.iou_sweep_batch(probs, st, st.masks, table, lo, thr)
+        else:
+            batches = [[records[i] for i in indices[lo:lo + images_per_batch]] for lo in range(0, len(indices), images_per_batch)]
+            total = sum(len(r["sents"]) for b in batches for r in b)
+            table = torch.zeros(total, T, 2, dtype=torch.int32, device=self.device)
+            row0 = 0
+            for recs in batches:
+                img, params = self.pipe(recs)
+                n = len(recs)
+                if n < images_per_batch:
+                    rep = torch.tensor(list(range(n)) + [n - 1] * (images_per_batch - n), device=self.device)
+                    img = img[rep]
+                sents = [s for p in params for s in p["sents"]]
+                index, masks, descs = plan_inference(self._masks(recs, params), [p["inverse"] for p in params],
+                                                     [len(p["sents"]) for p in params])
+                K = len(sents)
+                word = self.pipe.tok.tokenize(sents + [sents[-1]] * (len(index) - K), self.pipe.word_length, True)
+                word = word.to(self.device, non_blocking=True)
+                st = self._staging().pack(masks, descs).upload()
+                if self._segment is not None:
+                    logits = self._segment(img, word, index)
+                else:
+                    logits = self.model(img[torch.tensor(index, device=self.device)], word)
+                probs = evalpost.sigmoid_upsample(logits, img.shape[-2], img.shape[-1])
+                evalpost.iou_sweep_batch(probs, st, st.masks, table, row0, thr)
+                row0 += K
+        flat = table.cpu().reshape(total, 2 * T)                   # the pass's one host read
+        if split == "validate" or group is not None:               # (as validate gathers and inference does not)
+            flat = gather_counts(flat, group)
+        self.sweep_counts = flat.numpy().reshape(-1, T, 2)
+        return sweep_metrics(self.sweep_counts, thr)
 
     @staticmethod
     def _visualize(callback, recs, sents, index, st, counts, out):

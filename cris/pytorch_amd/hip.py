@@ -355,6 +355,7 @@ _SIGS = {
     "cris_threshold_iou": (I, [P, P, L, F, P, P]),
     "cris_eval_desc_fill": (I, [P, P, I, I, I, L, I, L, I]),
     "cris_eval_iou_batch": (I, [P, I, I, I, P, P, I, P, C.c_size_t, F, F, P, I, P, C.c_size_t, P]),
+    "cris_eval_iou_sweep_batch": (I, [P, I, I, I, P, P, I, P, C.c_size_t, P, I, F, P, I, P]),
     "cris_predict_masks_batch": (I, [P, I, I, I, P, P, I, F, F, P, I, P, C.c_size_t, P]),
     "cris_preprocess_batch": (I, [P, I, I, I, P, P, P, P, P, P, P, P]),
     "cris_gray_sum_batch": (I, [P, P, I, P, P]),

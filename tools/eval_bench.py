@@ -7,7 +7,10 @@
 
 The forward alone (graph replay on a resident batch) is timed for scale.  Writes the table as markdown.
 
-    python tools/eval_bench.py [--records 256] [--out profiles/eval_throughput.md]"""
+    python tools/eval_bench.py [--records 256] [--out profiles/eval_throughput.md]
+
+`--sweep [T]` measures the threshold sweep instead (sweep_main: one `iou_sweep_batch` launch against T `iou_batch` launches, a
+whole `Evaluator.sweep` pass against a whole `validate` pass) and writes profiles/eval_sweep.md."""
 import argparse
 import io
 import os
@@ -68,12 +71,121 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps
 
 
+def sweep_main(a, dev, recs, pipe, runner):
+    """--sweep T: on the fixed probabilities of one batch of 32 (descriptors and masks uploaded once), launches only:
+    (a) one `iou_batch`; (b) T `iou_batch` launches into T tables - the way to these numbers without the sweep kernel; (c) one
+    `iou_sweep_batch` at the T thresholds; (c1) the same at ONE threshold (the histogram path without the search).  Then (d) a
+    whole `Evaluator.validate` pass against a whole `Evaluator.sweep` pass over the same records."""
+    T = int(a.sweep)
+    if not 1 <= T <= evalpost.SWEEP_MAX:
+        raise SystemExit("--sweep T: 1 <= T <= %d" % evalpost.SWEEP_MAX)
+    thrs = evaluate.sweep_thresholds() if T == 19 else np.linspace(0.05, 0.95, T).astype(np.float32)
+    img, word, params = pipe(recs[:BATCH])
+    for _ in range(3):
+        logits = runner(img, word).clone()
+    masks_u8 = [pngdec.decode_gray(r["mask"]) for r in recs[:BATCH]]
+    st = evalpost.EvalStaging(dev).pack(*evaluate.plan_validate(masks_u8, [p["inverse"] for p in params])).upload()
+    probs = evalpost.sigmoid_upsample(logits, SIZE, SIZE)
+    one = torch.zeros(BATCH, 2, dtype=torch.int32, device=dev)
+    tables = [torch.zeros(BATCH, 2, dtype=torch.int32, device=dev) for _ in range(T)]
+    swept = torch.zeros(BATCH, T, 2, dtype=torch.int32, device=dev)
+    swept1 = torch.zeros(BATCH, 1, 2, dtype=torch.int32, device=dev)
+
+    def arm_a():
+        evalpost.iou_batch(probs, st, st.masks, one, 0, 0.35)
+
+    def arm_b():
+        for t, tab in zip(thrs, tables):
+            evalpost.iou_batch(probs, st, st.masks, tab, 0, float(t))
+
+    def arm_c():
+        evalpost.iou_sweep_batch(probs, st, st.masks, swept, 0, thrs)
+
+    def arm_c1():
+        evalpost.iou_sweep_batch(probs, st, st.masks, swept1, 0, [0.35])
+
+    arm_b()
+    arm_c()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(swept, torch.stack(tables, 1)))        # before the timed launches accumulate further
+    hist = swept.cpu().numpy().astype(np.int64)
+    pixels = sum(int(m.shape[0]) * int(m.shape[1]) for m in masks_u8)
+    middle = int(hist[:, 0].sum() - hist[:, -1].sum())             # pred_0 - pred_{T-1}  (pred_i = union_i + inter_i - gt)
+    arms = (arm_a, arm_b, arm_c, arm_c1)
+    calls = (200 * a.reps, 20 * a.reps, 200 * a.reps, 200 * a.reps)      # a timed window is >= 0.1 s of device work
+    for f in arms:
+        timed(f, 2)
+    t_arm = [[] for _ in arms]
+    for _ in range(ROUNDS):
+        for f, k, v in zip(arms, calls, t_arm):
+            for tab in [one, swept, swept1] + tables:              # (the launches accumulate: keep the int32 counts far from 2^31)
+                tab.zero_()
+            v.append(timed(f, k) * 1e3)
+    t_a, t_b, t_c, t_c1 = t_arm
+
+    ev = evaluate.Evaluator(runner, pipe)
+    ev.validate(recs[:2 * BATCH], batch_size=BATCH)                # warm-up: eager call, graph capture
+    ev.sweep(recs[:2 * BATCH], thrs, batch_size=BATCH)
+    p_val, p_sweep = [], []
+    for _ in range(ROUNDS):
+        t0 = time.perf_counter()
+        ev.validate(recs, batch_size=BATCH)
+        torch.cuda.synchronize()
+        p_val.append(len(recs) / (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        res = ev.sweep(recs, thrs, batch_size=BATCH)
+        torch.cuda.synchronize()
+        p_sweep.append(len(recs) / (time.perf_counter() - t0))
+
+    def row(name, v, unit):
+        return "| %s | %s | %.3f | %.3f | %.3f %s |" % (name, " ".join("%.3f" % x for x in v), min(v), max(v), statistics.median(v), unit)
+
+    def ratio(num, den):
+        r = [x / y for x, y in zip(num, den)]
+        return "%.2f (per round %s)" % (statistics.median(num) / statistics.median(den), " ".join("%.2f" % x for x in r))
+
+    med = statistics.median
+    lines = ["# Threshold sweep: T thresholds in one launch against T launches", "",
+             "`python tools/eval_bench.py --sweep %d --records %d --reps %d` on %s: R50, %dx%d, %d tokens, synthetic weights, HIP-graph"
+             % (T, a.records, a.reps, torch.cuda.get_device_name(0), SIZE, SIZE, WORD_LEN),
+             "replay; %d synthetic records (originals 416-544 x 576-704), batch %d, T = %d thresholds %.2f .. %.2f, %d rounds with the arms"
+             % (a.records, BATCH, T, thrs[0], thrs[-1], ROUNDS),
+             "interleaved.  Arms (a)-(c1) are launches only, on the resident probabilities, descriptors and masks of one batch of 32",
+             "(%d original-size pixels); each figure is the mean of %d back-to-back calls (%d for (b)) inside a host clock that ends in a"
+             % (pixels, calls[0], calls[1]),
+             "device synchronisation.  (d) is a whole pass (JPEG decode, letter-box, forward, post-processing, one host read).", "",
+             "| arm | rounds | min | max | median |", "|---|---|---|---|---|",
+             row("(a) one `iou_batch` launch, ms", t_a, "ms"),
+             row("(b) %d `iou_batch` launches into %d tables, ms" % (T, T), t_b, "ms"),
+             row("(c) one `iou_sweep_batch` launch at %d thresholds, ms" % T, t_c, "ms"),
+             row("(c1) one `iou_sweep_batch` launch at 1 threshold, ms", t_c1, "ms"),
+             row("(d) whole `Evaluator.validate` pass (one threshold), samples/s", p_val, "samples/s"),
+             row("(d) whole `Evaluator.sweep` pass (%d thresholds), samples/s" % T, p_sweep, "samples/s"), "",
+             "* (c) < (b): %s - median (b) / (c) = %s." % (med(t_c) < med(t_b), ratio(t_b, t_c)),
+             "* (c) / (a) = %s; (c1) / (a) = %s." % (ratio(t_c, t_a), ratio(t_c1, t_a)),
+             "* sweep pass / validate pass = %s in samples/s." % ratio(p_sweep, p_val),
+             "* Every column of the sweep table equals the single-threshold table of its threshold: %s." % same,
+             "* %d of the batch's %d pixels (%.2f %%) lie between the lowest and the highest threshold - the ones that take the"
+             % (middle, pixels, 100.0 * middle / pixels),
+             "  binary search and an LDS add; the others are counted in registers.",
+             "* Last sweep: best threshold by mean IoU %.2f (%.4f), by overall IoU %.2f (%.4f)."
+             % (res.best("iou") + res.best("overall_iou")), ""]
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_throughput.md"))
+    ap.add_argument("--sweep", type=int, nargs="?", const=19, default=None, metavar="T",
+                    help="measure the threshold sweep at T thresholds (default 19) instead; writes profiles/eval_sweep.md")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "eval_throughput.md" if a.sweep is None else "eval_sweep.md")
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU (nothing here is measured on the CPU)")
     dev = torch.device("cuda:0")
@@ -82,6 +194,8 @@ def main():
     pipe = records.RecordPipeline(SIZE, WORD_LEN, dev, mode="val", tokenizer=tok)
     clip, head = arch.specs_by_name("r50")
     runner = InferenceRunner(clip, head, arch.synthetic_state_dict(clip, head, 0), dev)
+    if a.sweep is not None:
+        return sweep_main(a, dev, recs, pipe, runner)
 
     # ---- (a) post-processing of one batch of 32 on fixed logits
     img, word, params = pipe(recs[:BATCH])
