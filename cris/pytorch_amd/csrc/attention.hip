@@ -165,7 +165,7 @@ __global__ void attn_bwd_dkv_lds_kernel(const cris_attn_params p);
 #define AL_WAVES 4                         // waves per block
 // 16-row groups per wave: a block covers 16 * AL_G * AL_WAVES = 64 rows.  Fixed at 1 since round 3; the kernels keep their
 // one-trip `g` loops and [AL_G] arrays because hipcc emits other code for them once the loops are written out
-// (profiles/strip_scaffolding.md), and these kernels have no per-element edge test that would cover a change.
+// (profiles/strip_scaffolding.md).  tests/test_attn_edges.py holds every kernel of this file to per-element bounds at the tile edges.
 #define AL_G 1
 #define AL_LDS_FWD (3 * 2 * 8192)
 #define AL_LDS_DQ (2 * 3 * 8192)
@@ -175,6 +175,15 @@ static bool attn_use_lds(const cris_attn_params& p, int loop_rows, bool key_mask
     return !p.causal && (key_mask_ok || !p.key_tokens) && loop_rows >= ATTN_LDS_MIN && (p.Lk_pad & 7) == 0 && ((uintptr_t)p.Q & 15) == 0 &&
            ((uintptr_t)p.K & 15) == 0 && ((uintptr_t)p.V & 15) == 0 && (size_t)p.B * p.Lk * p.ldk * 2 < (1UL << 31) &&
            (size_t)p.B * p.Lq * p.ldq * 2 < (1UL << 31) && (size_t)p.B * p.Hn * 64 * (p.Lk_pad > p.Lq_pad ? p.Lk_pad : p.Lq_pad) * 2 < (1UL << 31);
+}
+// one predicate per launcher: what the launcher branches on is what cris_attn_plan reports
+static bool attn_fwd_lds(const cris_attn_params& p) { return attn_use_lds(p, p.Lk); }
+static bool attn_bwd_dq_lds(const cris_attn_params& p) { return attn_use_lds(p, p.Lk); }
+// (the key side also serves the decoder's cross attention: 17 / 22 keys with a padding mask, but a 676 / 900-query loop)
+static bool attn_bwd_dkv_lds(const cris_attn_params& p) { return attn_use_lds(p, p.Lq, true) && (p.Lq_pad & 7) == 0; }
+extern "C" int cris_attn_plan(const cris_attn_params* pp, int which) {
+    CRIS_CHECK_ARG(pp && which >= 0 && which <= 2, "which is 0 (fwd), 1 (bwd_dq) or 2 (bwd_dkv)");
+    return which == 0 ? attn_fwd_lds(*pp) : which == 1 ? attn_bwd_dq_lds(*pp) : attn_bwd_dkv_lds(*pp);
 }
 static int attn_launch_lds(int which, const cris_attn_params& p, dim3 grid, void* stream) {
     static const int ready = (int)hipFuncSetAttribute((const void*)attn_bwd_dkv_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AL_LDS_DKV);
@@ -194,7 +203,7 @@ extern "C" int cris_attn_fwd(const cris_attn_params* pp, void* stream) {
     if (attn_check(p)) return -1;
     CRIS_CHECK_ARG(p.Vt && p.O && (p.ldo & 3) == 0, "forward operands");
     dim3 grid(cris_cdiv(p.Lq, 64), p.B * p.Hn);
-    if (attn_use_lds(p, p.Lk)) return attn_launch_lds(0, p, grid, stream);
+    if (attn_fwd_lds(p)) return attn_launch_lds(0, p, grid, stream);
     hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
     CRIS_LAUNCH_CHECK();
     return 0;
@@ -308,7 +317,7 @@ extern "C" int cris_attn_bwd_dq(const cris_attn_params* pp, void* stream) {
     CRIS_CHECK_ARG(p.V && p.Kt && p.O && p.dO && p.lse && p.delta && p.dQ, "backward(dq) operands");
     CRIS_CHECK_ARG((p.ldv & 7) == 0 && (p.lddo & 7) == 0 && (p.ldo & 7) == 0 && (p.lddq & 3) == 0, "ld");
     dim3 grid(cris_cdiv(p.Lq, 64), p.B * p.Hn);
-    if (attn_use_lds(p, p.Lk)) return attn_launch_lds(1, p, grid, stream);
+    if (attn_bwd_dq_lds(p)) return attn_launch_lds(1, p, grid, stream);
     hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
     CRIS_LAUNCH_CHECK();
     return 0;
@@ -420,8 +429,7 @@ extern "C" int cris_attn_bwd_dkv(const cris_attn_params* pp, void* stream) {
     CRIS_CHECK_ARG((p.ldv & 7) == 0 && (p.lddo & 7) == 0 && (p.lddk & 3) == 0 && (p.lddv & 3) == 0, "ld");
     CRIS_CHECK_ARG((p.Lq_pad & 3) == 0 && p.Lq_pad >= ((p.Lq + 31) / 32) * 32, "Lq_pad must cover whole 32-query tiles");
     dim3 grid(cris_cdiv(p.Lk, 64), p.B * p.Hn);
-    // (the key side also serves the decoder's cross attention: 17 / 22 keys with a padding mask, but a 676 / 900-query loop)
-    if (attn_use_lds(p, p.Lq, true) && (p.Lq_pad & 7) == 0) return attn_launch_lds(2, p, grid, stream);
+    if (attn_bwd_dkv_lds(p)) return attn_launch_lds(2, p, grid, stream);
     hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
     CRIS_LAUNCH_CHECK();
     return 0;

@@ -306,6 +306,7 @@ _SIGS = {
     "cris_attn_fwd": (I, [P, P]),
     "cris_attn_bwd_dq": (I, [P, P]),
     "cris_attn_bwd_dkv": (I, [P, P]),
+    "cris_attn_plan": (I, [P, I]),
     "cris_stem_im2col": (I, [P, I, I, I, P, P]),
     "cris_avgpool2_fwd": (I, [P, I, I, I, I, I, I, P, I, I, P]),
     "cris_avgpool2_bwd": (I, [P, I, I, I, I, I, I, P, I, I, I, P]),

@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -395,6 +395,10 @@ typedef struct {
 int cris_attn_fwd(const cris_attn_params* p, void* stream);
 int cris_attn_bwd_dq(const cris_attn_params* p, void* stream);
 int cris_attn_bwd_dkv(const cris_attn_params* p, void* stream);
+/* Which kernel a launcher takes for `p` (host arithmetic, no device call; the launchers branch on the same predicates):
+ * which = 0 cris_attn_fwd, 1 cris_attn_bwd_dq, 2 cris_attn_bwd_dkv.  Returns 0 = the direct kernel (operands straight from L2),
+ * 1 = the long-sequence kernel that stages 64-row tiles through LDS; -1 (cris_last_error) for any other `which`. */
+int cris_attn_plan(const cris_attn_params* p, int which);
 
 /* ------------------------------------------------------------------------------------------------
  * Elementwise / data movement kernels
