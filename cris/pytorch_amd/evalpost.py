@@ -15,7 +15,12 @@ packed into one pinned buffer (`EvalStaging`), the warped map never written, cou
 `predict_batch` is the same launch without ground truth (predict.Predictor): no mask goes up (`EvalStaging.pack_sizes`), the
 binary masks come out at the original sizes and (area, score, bounding box) accumulate in an int64 table (`new_predict_stats`).
 `iou_sweep_batch` is `iou_batch` at up to 64 thresholds in one launch (evaluate.Evaluator.sweep): counts [R, T, 2], column i what
-`iou_batch` counts at thresholds[i]."""
+`iou_batch` counts at thresholds[i].
+
+`Components` is the optional mask clean-up between the launch that writes the masks and the numbers read from them:
+`label_components` (connected-component labels of the packed masks, three launches), `filter_components` (keep the largest
+component / drop the small ones in place, statistics over the kept pixels, three launches) and `mask_iou_batch` (intersection /
+union counts from mask bytes) - DESIGN.md 9b."""
 import ctypes as C
 
 import numpy as np
@@ -249,3 +254,142 @@ def predict_batch(probs, descs, stats, row0, thr=0.35, out_masks=None, border=0.
     hip.call("cris_predict_masks_batch", ptr(probs), P, H, W, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n, float(thr),
              float(border), stats.data_ptr() + 48 * int(row0), stats.shape[0] - int(row0), ptr(out_masks),
              0 if out_masks is None else out_masks.numel(), _stream())
+
+
+class Components:
+    """Connected-component clean-up of a thresholded mask, as a validated value (the style of ops.SegLoss): components of fewer
+    than `min_area` pixels are dropped first; with keep="largest" only the remaining component of greatest area survives (ties:
+    the one whose first pixel in raster order comes first).  connectivity: 4 (edges) or 8 (edges and corners).  Host only."""
+
+    KEEP = ("all", "largest")
+    __slots__ = ("keep", "min_area", "connectivity")
+
+    def __init__(self, keep="all", min_area=0, connectivity=8):
+        if keep not in self.KEEP:
+            raise ValueError("Components: keep must be 'all' or 'largest', got %r" % (keep,))
+        if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or min_area < 0:
+            raise ValueError("Components: min_area must be an integer >= 0, got %r" % (min_area,))
+        if isinstance(connectivity, bool) or connectivity not in (4, 8):
+            raise ValueError("Components: connectivity must be 4 or 8, got %r" % (connectivity,))
+        object.__setattr__(self, "keep", keep)
+        object.__setattr__(self, "min_area", int(min_area))
+        object.__setattr__(self, "connectivity", int(connectivity))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Components is immutable")
+
+    @property
+    def is_noop(self):
+        """keep="all" with min_area <= 1 filters nothing (every component has at least one pixel)"""
+        return self.keep == "all" and self.min_area <= 1
+
+    def __eq__(self, other):
+        return isinstance(other, Components) and (self.keep, self.min_area, self.connectivity) == (other.keep, other.min_area, other.connectivity)
+
+    def __hash__(self):
+        return hash((self.keep, self.min_area, self.connectivity))
+
+    def __repr__(self):
+        return "Components(keep=%r, min_area=%d, connectivity=%d)" % (self.keep, self.min_area, self.connectivity)
+
+
+def components_spec(value, what="components"):
+    """None or a Components -> the spec to apply, or None when there is nothing to do (a spec that filters nothing is no spec);
+    anything else is a ValueError.  Host only: callers run this before they touch a device."""
+    if value is None:
+        return None
+    if not isinstance(value, Components):
+        raise ValueError("%s must be None or an evalpost.Components, got %r" % (what, value))
+    return None if value.is_noop else value
+
+
+INFO_FIELDS = ("n_components", "kept_components", "raw_area", "error")
+LABEL_ERROR = -2        # CC_ERR of csrc/evalpost.hip: a union-find walk hit its iteration cap
+
+
+def _check_packed(name, masks_u8, descs):
+    if masks_u8.device.type != "cuda":
+        raise RuntimeError("evalpost runs on the GPU only (no CPU fallback)")
+    if masks_u8.dtype != torch.uint8 or masks_u8.dim() != 1 or not masks_u8.is_contiguous() or masks_u8.numel() < descs.out_bytes:
+        raise ValueError("%s: masks_u8 must be a contiguous uint8 buffer of at least descs.out_bytes" % name)
+
+
+def label_components(masks_u8, descs, connectivity=8, out=None):
+    """Canonical connected-component labels of every descriptor's mask in the packed buffer `masks_u8` (what iou_batch /
+    predict_batch wrote into out_masks; `descs`: the uploaded EvalStaging of that launch) -> int32 [descs.out_bytes], one word per
+    mask byte at the same offsets: the word of a foreground pixel (byte != 0, x < w_out) is the index y * pitch + x, relative to
+    the descriptor's out_off, of the first pixel of its component in raster order; background and pitch padding are -1; words
+    between two descriptors' rectangles are not written.  Three launches on the current stream (cris_label_components), none
+    depending on the content.  out: an int32 buffer of at least descs.out_bytes words to reuse."""
+    _check_packed("label_components", masks_u8, descs)
+    if connectivity not in (4, 8):
+        raise ValueError("label_components: connectivity must be 4 or 8, got %r" % (connectivity,))
+    if out is None:
+        out = torch.empty(descs.out_bytes, dtype=torch.int32, device=masks_u8.device)
+    elif out.dtype != torch.int32 or out.dim() != 1 or not out.is_contiguous() or out.numel() < descs.out_bytes or out.device != masks_u8.device:
+        raise ValueError("label_components: out must be a contiguous int32 buffer of at least descs.out_bytes words on the masks' device")
+    hip.call("cris_label_components", ptr(masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n,
+             int(connectivity), ptr(out), out.numel(), _stream())
+    return out[:descs.out_bytes]
+
+
+def filter_work(descs, device, out=None):
+    """the scratch of `filter_components` for this batch (areas per root, one winner word per descriptor): `out` when it is large
+    enough, a new int64 buffer otherwise.  The launcher zeroes it itself."""
+    words = (hip.load().cris_filter_components_work_bytes(descs.out_bytes, descs.n) + 7) // 8
+    if out is not None and out.numel() >= words:
+        return out
+    return torch.empty(words + words // 4, dtype=torch.int64, device=device)
+
+
+def filter_components(masks_u8, labels, descs, spec, info, row0, probs=None, stats=None, border=0.0, work=None):
+    """Apply `spec` (a Components) to the packed masks IN PLACE, given their `label_components` labels: kept pixels become 255,
+    every other byte of a descriptor's rectangle 0.  info: [R, 4] cuda int64 zeroed by the caller once per pass;
+    info[row0 + row] += (n_components before filtering, kept_components, raw_area, error) (INFO_FIELDS).  probs / stats (both or
+    neither; probs [P, H, W] as for predict_batch, stats from new_predict_stats): stats[row0 + row] receives over the KEPT pixels
+    exactly what predict_batch adds over the pixels above its threshold - the value is recomputed by the same device function, so a
+    mask of one component gives predict_batch's row bit for bit.  work: scratch from `filter_work` to reuse.  One memset and three
+    launches on the current stream (cris_filter_components).  The caller checks the error column when it reads `info`."""
+    _check_packed("filter_components", masks_u8, descs)
+    if not isinstance(spec, Components):
+        raise ValueError("filter_components: spec must be an evalpost.Components, got %r" % (spec,))
+    if labels.dtype != torch.int32 or labels.dim() != 1 or not labels.is_contiguous() or labels.numel() < descs.out_bytes:
+        raise ValueError("filter_components: labels must be a contiguous int32 buffer of at least descs.out_bytes words")
+    if info.dtype != torch.int64 or info.dim() != 2 or info.shape[1] != 4 or not info.is_contiguous() or not 0 <= row0 < info.shape[0]:
+        raise ValueError("filter_components: info must be contiguous int64 [R, 4] and row0 inside it")
+    if (probs is None) != (stats is None):
+        raise ValueError("filter_components: probs and stats go together")
+    P = H = W = 0
+    if probs is not None:
+        if probs.dim() != 3 or probs.dtype != torch.float32 or not probs.is_contiguous():
+            raise ValueError("filter_components: probs must be contiguous fp32 [P, H, W]")
+        if stats.dtype != torch.int64 or stats.dim() != 2 or stats.shape[1] != 6 or not stats.is_contiguous() or not 0 <= row0 < stats.shape[0]:
+            raise ValueError("filter_components: stats must be contiguous int64 [R, 6] and row0 inside it")
+        P, H, W = probs.shape
+    work = filter_work(descs, masks_u8.device, work)
+    hip.call("cris_filter_components", ptr(masks_u8), descs.out_bytes, ptr(labels), labels.numel(), C.addressof(descs.descs),
+             descs.dev.data_ptr(), descs.n, 1 if spec.keep == "largest" else 0, min(spec.min_area, 2 ** 31 - 1), ptr(work), 8 * work.numel(),
+             info.data_ptr() + 32 * int(row0), info.shape[0] - int(row0), ptr(probs), P, H, W, float(border),
+             None if stats is None else stats.data_ptr() + 48 * int(row0), 0 if stats is None else stats.shape[0] - int(row0), _stream())
+
+
+def check_component_info(info):
+    """info: the [R, 4] table of `filter_components` as read by the host -> the same array; raises when an error column is set"""
+    info = np.asarray(info)
+    bad = np.nonzero(info[:, 3])[0]
+    if bad.size:
+        raise RuntimeError("connected components: the union-find walk of row(s) %s hit its iteration cap (corrupt label buffer?)" % bad[:8].tolist())
+    return info
+
+
+def mask_iou_batch(pred_masks_u8, descs, gt_masks_u8, counts, row0):
+    """counts[row0 + row] += (#(pred != 0 and gt != 0), #(pred != 0 or gt != 0)) per descriptor, from mask BYTES
+    (cris_mask_iou_batch): pred in the packed output layout (out_off), gt the staging's packed masks (mask_off).  counts: [R, 2] cuda
+    int32, iou_batch's table - on iou_batch's own unfiltered out_masks this reproduces its counts."""
+    _check_packed("mask_iou_batch", pred_masks_u8, descs)
+    if gt_masks_u8.dtype != torch.uint8 or not gt_masks_u8.is_contiguous():
+        raise ValueError("mask_iou_batch: gt_masks_u8 must be a contiguous uint8 buffer")
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != 2 or not counts.is_contiguous() or not 0 <= row0 < counts.shape[0]:
+        raise ValueError("mask_iou_batch: counts must be contiguous int32 [R, 2] and row0 inside it")
+    hip.call("cris_mask_iou_batch", ptr(pred_masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n,
+             ptr(gt_masks_u8), gt_masks_u8.numel(), counts.data_ptr() + 8 * int(row0), counts.shape[0] - int(row0), _stream())

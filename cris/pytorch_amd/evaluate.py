@@ -13,6 +13,10 @@ read ONCE, after the last batch - no batch waits for the host (a `visualize` cal
 
 `Evaluator.sweep` is either pass at many thresholds at once (`evalpost.iou_sweep_batch`, a [n, T, 2] table): `sweep_metrics` turns
 the table into a `SweepResult` - IoU, overall IoU and Pr@X per threshold, the best threshold - whose column t equals the pass at thr=t.
+
+`validate` / `inference` take `components=evalpost.Components(...)`: every predicted mask is cleaned up on the device (connected
+components) before it is counted - `iou_batch` writes the masks, `label_components` / `filter_components` rewrite them
+in place and `evalpost.mask_iou_batch` adds the counts of the filtered masks to the pass's table.
 """
 import math
 
@@ -168,7 +172,8 @@ class Evaluator:
         self._segment = getattr(model, "segment", None) or getattr(model, "segment_expressions", None)
         self._ring = [evalpost.EvalStaging(self.device) for _ in range(self.RING)]
         self._turn = 0
-        self.per_sample = self.counts = self.sweep_counts = None
+        self.per_sample = self.counts = self.sweep_counts = self.component_info = None
+        self._cc_masks = self._cc_labels = self._cc_work = self._cc_counts = None      # component clean-up scratch, reused across batches
 
     def _staging(self):
         self._turn = (self._turn + 1) % self.RING
@@ -182,6 +187,28 @@ class Evaluator:
                 raise ValueError("record %s: mask is %s, image %s" % (p["mask_dir"], tuple(m.shape), tuple(p["ori_size"])))
         return masks
 
+    def _clean_counts(self, spec, probs, st, table, row0, info, out=None):
+        """one batch with a Components spec: iou_batch writes the masks (its own counts go to a scratch table), the filter rewrites
+        them in place, mask_iou_batch adds the filtered masks' counts to `table`.  out=None: an internal, reused mask buffer."""
+        if out is None:
+            if self._cc_masks is None or self._cc_masks.numel() < st.out_bytes:
+                self._cc_masks = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.uint8, device=self.device)
+            out = self._cc_masks
+        if self._cc_labels is None or self._cc_labels.numel() < st.out_bytes:
+            self._cc_labels = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.int32, device=self.device)
+        if self._cc_counts is None or self._cc_counts.shape[0] < table.shape[0] - row0:
+            self._cc_counts = torch.zeros(table.shape[0] - row0, 2, dtype=torch.int32, device=self.device)
+        self._cc_work = evalpost.filter_work(st, self.device, self._cc_work)
+        evalpost.iou_batch(probs, st, st.masks, self._cc_counts, 0, self.thr, out_masks=out)
+        labels = evalpost.label_components(out, st, spec.connectivity, out=self._cc_labels)
+        evalpost.filter_components(out, labels, st, spec, info, row0, work=self._cc_work)
+        evalpost.mask_iou_batch(out, st, st.masks, table, row0)
+        return out
+
+    def _finish_components(self, info, n):
+        """the pass's read of the component table (after the counts'): raises when an error column is set"""
+        self.component_info = evalpost.check_component_info(info[:n].cpu().numpy())
+
     def _finish(self, table, n, group):
         counts = gather_counts(table[:n].cpu(), group)             # the pass's one host read
         iou, prec, per = metrics(counts.numpy())
@@ -190,13 +217,17 @@ class Evaluator:
         return iou, prec
 
     @torch.no_grad()
-    def validate(self, records, indices=None, batch_size=32, group=None):
+    def validate(self, records, indices=None, batch_size=32, group=None, components=None):
+        """components: None or an evalpost.Components - clean every predicted mask up before it is counted (`component_info`
+        then holds the [n, 4] table of evalpost.INFO_FIELDS per sample)"""
+        spec = evalpost.components_spec(components, "validate: components")
         if self.pipe.mode != "val":
             raise ValueError("validate needs a RecordPipeline in mode 'val'")
         indices = list(range(len(records))) if indices is None else [int(i) for i in indices]
         if not indices:
             raise ValueError("validate: no records")
         table = torch.zeros(len(indices), 2, dtype=torch.int32, device=self.device)
+        info = None if spec is None else torch.zeros(len(indices), 4, dtype=torch.int64, device=self.device)
         for lo in range(0, len(indices), batch_size):
             recs = [records[i] for i in indices[lo:lo + batch_size]]
             img, word, params = self.pipe(recs)
@@ -206,11 +237,19 @@ class Evaluator:
                 img, word = img[rep], word[rep]
             st = self._staging().pack(*plan_validate(self._masks(recs, params), [p["inverse"] for p in params])).upload()
             probs = evalpost.sigmoid_upsample(self.model(img, word), img.shape[-2], img.shape[-1])
-            evalpost.iou_batch(probs, st, st.masks, table, lo, self.thr)
-        return self._finish(table, len(indices), group)
+            if spec is None:
+                evalpost.iou_batch(probs, st, st.masks, table, lo, self.thr)
+            else:
+                self._clean_counts(spec, probs, st, table, lo, info)
+        result = self._finish(table, len(indices), group)
+        if spec is not None:
+            self._finish_components(info, len(indices))
+        return result
 
     @torch.no_grad()
-    def inference(self, records, indices=None, images_per_batch=8, visualize=None):
+    def inference(self, records, indices=None, images_per_batch=8, visualize=None, components=None):
+        """components: as for `validate`; a `visualize` callback then receives the FILTERED masks and their IoUs"""
+        spec = evalpost.components_spec(components, "inference: components")
         if self.pipe.mode != "test":
             raise ValueError("inference needs a RecordPipeline in mode 'test'")
         indices = list(range(len(records))) if indices is None else [int(i) for i in indices]
@@ -219,6 +258,7 @@ class Evaluator:
         batches = [[records[i] for i in indices[lo:lo + images_per_batch]] for lo in range(0, len(indices), images_per_batch)]
         total = sum(len(r["sents"]) for b in batches for r in b)
         table = torch.zeros(total, 2, dtype=torch.int32, device=self.device)
+        info = None if spec is None else torch.zeros(total, 4, dtype=torch.int64, device=self.device)
         row0 = 0
         for recs in batches:
             img, params = self.pipe(recs)
@@ -239,11 +279,17 @@ class Evaluator:
                 logits = self.model(img[torch.tensor(index, device=self.device)], word)
             probs = evalpost.sigmoid_upsample(logits, img.shape[-2], img.shape[-1])
             out = None if visualize is None else torch.empty(st.out_bytes, dtype=torch.uint8, device=self.device)
-            evalpost.iou_batch(probs, st, st.masks, table, row0, self.thr, out_masks=out)
+            if spec is None:
+                evalpost.iou_batch(probs, st, st.masks, table, row0, self.thr, out_masks=out)
+            else:
+                out = self._clean_counts(spec, probs, st, table, row0, info, out)
             if visualize is not None:
                 self._visualize(visualize, recs, sents, index, st, table[row0:row0 + K].cpu().numpy(), out.cpu().numpy())
             row0 += K
-        return self._finish(table, total, None)
+        result = self._finish(table, total, None)
+        if spec is not None:
+            self._finish_components(info, total)
+        return result
 
     @torch.no_grad()
     def sweep(self, records, thresholds=None, split="validate", indices=None, batch_size=32, images_per_batch=8, group=None):

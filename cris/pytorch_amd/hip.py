@@ -358,6 +358,10 @@ _SIGS = {
     "cris_eval_iou_batch": (I, [P, I, I, I, P, P, I, P, C.c_size_t, F, F, P, I, P, C.c_size_t, P]),
     "cris_eval_iou_sweep_batch": (I, [P, I, I, I, P, P, I, P, C.c_size_t, P, I, F, P, I, P]),
     "cris_predict_masks_batch": (I, [P, I, I, I, P, P, I, F, F, P, I, P, C.c_size_t, P]),
+    "cris_label_components": (I, [P, C.c_size_t, P, P, I, I, P, C.c_size_t, P]),
+    "cris_filter_components_work_bytes": (C.c_size_t, [C.c_size_t, I]),
+    "cris_filter_components": (I, [P, C.c_size_t, P, C.c_size_t, P, P, I, I, I, P, C.c_size_t, P, I, P, I, I, I, F, P, I, P]),
+    "cris_mask_iou_batch": (I, [P, C.c_size_t, P, P, I, P, C.c_size_t, P, I, P]),
     "cris_preprocess_batch": (I, [P, I, I, I, P, P, P, P, P, P, P, P]),
     "cris_gray_sum_batch": (I, [P, P, I, P, P]),
     "cris_preprocess_batch_aug": (I, [P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),

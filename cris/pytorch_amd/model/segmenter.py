@@ -619,14 +619,15 @@ class CRIS(nn.Module):
         from ..evaluate import Evaluator
         return Evaluator(self, pipeline, thr=thr)
 
-    def predictor(self, pipeline, thr=0.35):
+    def predictor(self, pipeline, thr=0.35, components=None):
         """Masks, boxes and scores for images WITHOUT ground truth from this module (eval mode only):
         `model.predictor(records.RecordPipeline(size, word_len, device, mode="test")).predict(images, expressions)`.  A
-        predict.Predictor bound to the eval forward and, for several expressions per image, to segment_expressions."""
+        predict.Predictor bound to the eval forward and, for several expressions per image, to segment_expressions.
+        components: the predictor's default mask clean-up (evalpost.Components) or None."""
         if self.training:
             raise RuntimeError("predictor is an inference object: put the model in eval() mode first")
         from ..predict import Predictor
-        return Predictor(self, pipeline, thr=thr)
+        return Predictor(self, pipeline, thr=thr, components=components)
 
     def _infer_runner(self, img):
         """the inference runner on the engine's tensors, refolded when the parameters / running statistics changed"""

@@ -13,7 +13,11 @@ up; the table of the whole call comes back once at the end, the masks once per b
 `evaluate.Evaluator.inference` (a short last image batch repeats its last image, the expression count is padded to a multiple of
 8 by repeating the last expression), so one graph is captured per shape.
 
-    python -m cris.pytorch_amd.predict --weights CKPT --config YAML --image F --expr "the left one" --out-prefix P
+`components=evalpost.Components(keep="largest", min_area=N)` cleans every mask up on the device before its numbers are taken
+(connected components: DESIGN.md 9b): the masks of a batch stay in a device buffer, `evalpost.label_components` and
+`evalpost.filter_components` run on the stream, and the call returns ComponentPrediction - area, box and score of the KEPT pixels.
+
+    python -m cris.pytorch_amd.predict --weights CKPT --config YAML --image F --expr "the left one" --out-prefix P [--keep largest]
 """
 from collections import namedtuple
 
@@ -26,6 +30,11 @@ Prediction = namedtuple("Prediction", "sentence mask area box score")
 Prediction.__doc__ = """sentence: the expression; mask: uint8 [h, w] of 0 / 255 at the image's own size (numpy array, CUDA tensor view or
 None: `masks`); area: pixels above the threshold; box: (x0, y0, x1, y1) half-open, None when area == 0; score: the mean warped
 probability over those pixels, score_q16 / (65536 * area) in float64 (each pixel's value rounded to 1 / 65536), 0.0 when area == 0"""
+
+ComponentPrediction = namedtuple("ComponentPrediction", "sentence mask area box score n_components raw_area")
+ComponentPrediction.__doc__ = """what `predict` returns with a `components` spec: sentence, mask, area, box, score as in Prediction but over
+the KEPT pixels (mask: the filtered mask); n_components: connected components of the thresholded mask BEFORE filtering; raw_area: its
+pixels before filtering (what Prediction.area would have been).  Nothing kept: area 0, box None, score 0.0"""
 
 BatchPlan = namedtuple("BatchPlan", "lo n image_index index descs")
 BatchPlan.__doc__ = """images lo .. lo + n of the call; image_index: the batch's images padded to images_per_batch by repeating the last
@@ -64,6 +73,13 @@ def plan_predict(sents_per_image, images_per_batch=8, multiple=8, inverses=None)
     return plans
 
 
+def _check_components(value, default):
+    """the spec of one call: "default" -> the constructor's; None / a no-op spec -> None (host only)"""
+    if isinstance(value, str) and value == "default":
+        return default
+    return evalpost.components_spec(value, "predict: components")
+
+
 def _check_inputs(images, expressions, images_per_batch, masks):
     """-> (kind 'bytes' / 'array', expressions as lists); everything here is host-only"""
     if masks not in MASK_MODES:
@@ -94,23 +110,26 @@ def _check_inputs(images, expressions, images_per_batch, masks):
 
 
 class Predictor:
-    """`Predictor(model, pipeline, thr=0.35)`: model - an InferenceRunner, the drop-in CRIS module in eval mode, or any callable
+    """`Predictor(model, pipeline, thr=0.35, components=None)`: model - an InferenceRunner, the drop-in CRIS module in eval mode, or any callable
     `(img, word) -> logits [B, 1, h, w]`; when it offers `segment(img, word, image_index)` or `segment_expressions`, the visual
     encoder runs once per image, otherwise `model(img[index], word)` is called.  pipeline - a RecordPipeline in mode "test" (its
-    preprocessor, tokenizer, word length and decode threads are used; no record is needed)."""
+    preprocessor, tokenizer, word length and decode threads are used; no record is needed).  components - None or an
+    evalpost.Components: the mask clean-up `predict` applies unless the call names another."""
 
     RING = 3            # descriptor staging buffers in flight (evaluate.Evaluator.RING)
 
-    def __init__(self, model, pipeline, thr=0.35):
+    def __init__(self, model, pipeline, thr=0.35, components=None):
         if getattr(pipeline, "mode", None) != "test":
             raise ValueError("Predictor needs a RecordPipeline in mode 'test', got %r" % (getattr(pipeline, "mode", None),))
         thr = float(thr)
         if not 0.0 <= thr < float("inf"):
             raise ValueError("Predictor: thr must be finite and >= 0, got %r" % (thr,))
         self.model, self.pipe, self.thr = model, pipeline, thr
+        self.components = evalpost.components_spec(components, "Predictor: components")
         self.device = pipeline.device
         self._segment = getattr(model, "segment", None) or getattr(model, "segment_expressions", None)
         self._ring, self._turn = None, 0
+        self._cc_masks = self._cc_labels = self._cc_work = None       # component clean-up scratch, reused across batches
 
     def _staging(self):
         if self._ring is None:          # (the first device allocation: after every argument check)
@@ -118,18 +137,37 @@ class Predictor:
         self._turn = (self._turn + 1) % self.RING
         return self._ring[self._turn]
 
+    def _component_buffers(self, st, out):
+        """the mask buffer of a batch that is cleaned up (out=None: an internal one that never leaves the device) and the label /
+        work scratch, grown when a batch needs more and reused otherwise"""
+        if out is None:
+            if self._cc_masks is None or self._cc_masks.numel() < st.out_bytes:
+                self._cc_masks = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.uint8, device=self.device)
+            out = self._cc_masks
+        if self._cc_labels is None or self._cc_labels.numel() < st.out_bytes:
+            self._cc_labels = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.int32, device=self.device)
+        self._cc_work = evalpost.filter_work(st, self.device, self._cc_work)
+        return out
+
     @torch.no_grad()
-    def predict(self, images, expressions, images_per_batch=8, masks="host"):
+    def predict(self, images, expressions, images_per_batch=8, masks="host", components="default"):
         """images: JPEG bytes per image, or uint8 RGB [h, w, 3] arrays / tensors per image (one kind per call; JPEG files come
         back turned by their EXIF orientation, as cv2.imdecode returns them).  expressions: per image a str or a non-empty list
         of str.  masks: "host" (numpy arrays, one device-to-host copy per batch), "device" (views of one CUDA buffer per batch)
-        or None (statistics only: no mask buffer is allocated).  Returns a list per image of Prediction per expression."""
+        or None (statistics only: no mask buffer is allocated).  Returns a list per image of Prediction per expression.
+        components: an evalpost.Components, None (no clean-up) or "default" (the constructor's).  With a spec every mask is
+        labelled and filtered on the device before anything is read, the statistics are those of the kept pixels and the entries
+        are ComponentPrediction; with masks=None the masks live in an internal device buffer and never reach the host."""
         from . import jpegdec
+        spec = _check_components(components, self.components)
         kind, images, exprs = _check_inputs(images, expressions, images_per_batch, masks)
         images_per_batch = int(images_per_batch)
         plans = plan_predict([len(e) for e in exprs], images_per_batch)
         total = sum(len(e) for e in exprs)
         table = evalpost.new_predict_stats(total, self.device)
+        if spec is not None:
+            ktable = evalpost.new_predict_stats(total, self.device)    # statistics of the kept pixels
+            info = torch.zeros(total, 4, dtype=torch.int64, device=self.device)
         kept = []                                                      # per expression: its mask (or None)
         for b in plans:
             part = images[b.lo:b.lo + b.n]
@@ -150,7 +188,12 @@ class Predictor:
                 logits = self.model(img[torch.tensor(b.index, device=self.device)], word)
             probs = evalpost.sigmoid_upsample(logits, img.shape[-2], img.shape[-1])
             out = None if masks is None else torch.empty(st.out_bytes, dtype=torch.uint8, device=self.device)
+            if spec is not None:
+                out = self._component_buffers(st, out)
             evalpost.predict_batch(probs, st, table, 0, self.thr, out_masks=out)
+            if spec is not None:
+                labels = evalpost.label_components(out, st, spec.connectivity, out=self._cc_labels)
+                evalpost.filter_components(out, labels, st, spec, info, 0, probs=probs, stats=ktable, work=self._cc_work)
             if masks is None:
                 kept += [None] * K
                 continue
@@ -159,6 +202,8 @@ class Predictor:
                 d = st.descs[k]
                 m = buf[d.out_off:d.out_off + d.pitch * d.h_out].reshape(d.h_out, d.pitch)[:, :d.w_out]
                 kept.append(np.ascontiguousarray(m) if masks == "host" else m)
+        if spec is not None:
+            return self._component_result(exprs, kept, torch.cat([ktable, info, table[:, :1]], 1).cpu().numpy())
         stats = table.cpu().numpy()                                    # the call's one read of the statistics
         result, k = [], 0
         for e in exprs:
@@ -166,6 +211,24 @@ class Predictor:
             for s in e:
                 area, q16, x0, y0, x1, y1 = (int(v) for v in stats[k])
                 row.append(Prediction(s, kept[k], area, (x0, y0, x1, y1) if area else None, q16 / (65536.0 * area) if area else 0.0))
+                k += 1
+            result.append(row)
+        return result
+
+
+    @staticmethod
+    def _component_result(exprs, kept, rows):
+        """rows: [total, 11] = kept statistics (6), info (4), raw area - the call's one read, the error column checked here"""
+        evalpost.check_component_info(rows[:, 6:10])
+        result, k = [], 0
+        for e in exprs:
+            row = []
+            for s in e:
+                area, q16, x0, y0, x1, y1, n_comp, _, raw, _, raw_stats = (int(v) for v in rows[k])
+                if raw != raw_stats:
+                    raise RuntimeError("predict: the labelled foreground (%d pixels) is not the thresholded mask (%d)" % (raw, raw_stats))
+                row.append(ComponentPrediction(s, kept[k], area, (x0, y0, x1, y1) if area else None,
+                                               q16 / (65536.0 * area) if area else 0.0, n_comp, raw))
                 k += 1
             result.append(row)
         return result
@@ -217,7 +280,15 @@ def main(argv=None):
     ap.add_argument("--synthetic", nargs="?", const="r50", default=None, metavar="SPEC",
                     help="arch.synthetic_state_dict of r50 (default), r101 or tiny instead of --weights / --config")
     ap.add_argument("--size", type=int, default=None, help="network input size (default: the config's input_size, 416)")
+    ap.add_argument("--keep", choices=evalpost.Components.KEEP, default="all",
+                    help="connected-component clean-up of every mask: 'largest' keeps the largest component only")
+    ap.add_argument("--min-area", type=int, default=0, metavar="N", help="drop components of fewer than N pixels")
+    ap.add_argument("--connectivity", type=int, choices=(4, 8), default=8, help="pixels connect through edges (4) or edges and corners (8)")
     a = ap.parse_args(argv)
+    try:
+        spec = evalpost.Components(a.keep, a.min_area, a.connectivity)
+    except ValueError as e:
+        ap.error(str(e))
     if not torch.cuda.is_available():
         raise SystemExit("predict needs a GPU (there is no CPU fallback)")
     dev = torch.device("cuda:0")
@@ -243,12 +314,13 @@ def main(argv=None):
     with open(a.image, "rb") as f:
         data = f.read()
     image = data if data[:2] == b"\xff\xd8" else np.array(Image.open(a.image).convert("RGB"))
-    out = Predictor(runner, pipe, thr=a.thr).predict([image], [a.expr], images_per_batch=1, masks="host")[0]
+    out = Predictor(runner, pipe, thr=a.thr, components=spec).predict([image], [a.expr], images_per_batch=1, masks="host")[0]
     os.makedirs(os.path.dirname(os.path.abspath(a.out_prefix)), exist_ok=True)
     for j, p in enumerate(out):
         path = "%s_%d.png" % (a.out_prefix, j)
         Image.fromarray(p.mask, "L").save(path)
-        print("%s\t%r\tbox %s\tarea %d\tscore %.4f" % (path, p.sentence, p.box, p.area, p.score))
+        extra = "\tcomponents %d\traw area %d" % (p.n_components, p.raw_area) if isinstance(p, ComponentPrediction) else ""
+        print("%s\t%r\tbox %s\tarea %d\tscore %.4f%s" % (path, p.sentence, p.box, p.area, p.score, extra))
     return out
 
 

@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -554,6 +554,38 @@ int cris_eval_iou_sweep_batch(const float* probs, int P, int H, int W, const cri
 int cris_predict_masks_batch(const float* probs, int P, int H, int W, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev,
                              int n, float thr, float border, long long* stats, int stat_rows, unsigned char* out_masks, size_t out_bytes,
                              void* stream);
+/* Connected components of the packed masks those launches write (mask clean-up before the statistics: keep the largest component, drop
+ * the small ones).  masks: the out_masks buffer (descriptor d at d.out_off, d.h_out rows of d.pitch bytes); a pixel is foreground iff
+ * its byte is != 0 and x < w_out, the pitch padding is background and never a neighbour.  labels: one int32 word per mask byte, same
+ * offsets; after cris_label_components the word of a foreground pixel is its CANONICAL label, the index y * pitch + x (relative to
+ * out_off) of the first pixel of its component in raster order, and background and padding are -1 (-2 marks a pixel whose union-find
+ * walk hit its iteration cap: never with intact buffers).  connectivity: 4 or 8.  Three launches (32 x 32 tiles in LDS, merges across
+ * tile borders, flatten) on the stream, none depending on the mask's content.  Checked on the host before the first launch: operands
+ * non-NULL, n in 1 .. 65535, connectivity, alignment, label_words >= mask_bytes, and per descriptor sizes, pitch and out_off inside
+ * mask_bytes (map, row and mask_off are ignored). */
+int cris_label_components(const unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev,
+                          int n, int connectivity, int* labels, size_t label_words, void* stream);
+/* Filter by those labels, in place: components of area < min_area are dropped first; with keep_largest the remaining component of
+ * greatest area alone survives (ties: the lowest canonical label).  Kept bytes become 255, every other byte of the rectangle 0.
+ * info: int64 table [info_rows][4], descriptor d adds to row d.row (n_components before filtering, kept_components, raw_area = foreground
+ * pixels before filtering, error = 1 when a label carries the cap mark); the caller zeroes it.  probs / stats (both or neither): over the
+ * KEPT pixels stats[d.row] receives exactly what cris_predict_masks_batch adds per pixel above its threshold (the value is recomputed by
+ * the same device function), so for a mask of one component the row equals that launch's row bit for bit; stats rows are initialised
+ * as for that launch.  work: device scratch of cris_filter_components_work_bytes bytes (areas per root, one winner word per
+ * descriptor), zeroed here by a memset on the stream; then three launches (areas, winner by one 64-bit atomicMax of
+ * (area << 32) | (0xffffffff - label), filter).  Integer atomics only: the same masks and tables on every run.  Checked on the host
+ * first: operands, n, keep_largest, min_area >= 0, alignment, label_words, work_bytes, row < min(info_rows, stat_rows), map < P with
+ * probs, and per descriptor what cris_label_components checks. */
+size_t cris_filter_components_work_bytes(size_t mask_bytes, int n);
+int cris_filter_components(unsigned char* masks, size_t mask_bytes, const int* labels, size_t label_words, const cris_eval_desc* descs_host,
+                           const cris_eval_desc* descs_dev, int n, int keep_largest, int min_area, void* work, size_t work_bytes,
+                           long long* info, int info_rows, const float* probs, int P, int H, int W, float border, long long* stats,
+                           int stat_rows, void* stream);
+/* counts[d.row] += (#(pred != 0 && gt != 0), #(pred != 0 || gt != 0)) over x < w_out, from mask BYTES: pred at d.out_off of `pred`
+ * (filtered or not), gt at d.mask_off of `gt`, both with d.pitch.  The int32 [count_rows][2] table and the integer atomics of
+ * cris_eval_iou_batch: on its unfiltered out_masks this launch reproduces its counts. */
+int cris_mask_iou_batch(const unsigned char* pred, size_t pred_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev,
+                        int n, const unsigned char* gt, size_t gt_bytes, int* counts, int count_rows, void* stream);
 /* ---- input preprocessing (reference utils/dataset.py:146-168 RefDataset.__getitem__, :207-221 convert; csrc/inputpipe.hip) ----
  * One launch per batch: img_out[b] = ((cv2.warpAffine(rgb_u8, mat, (S_w, S_h), INTER_CUBIC, borderValue=border_rgb).float()
  * / 255 - mean) / std) as [3][S_h][S_w] (through lut_img [3][256]), mask_out[b] = cv2.warpAffine(mask_u8, mat, ...,

@@ -9,7 +9,15 @@
 Each arm 5 rounds, interleaved; every figure is a host clock around work that ends with its results on the host.  Writes the
 table as markdown.
 
-    python tools/predict_bench.py [--reps 5] [--out profiles/predict.md]"""
+    python tools/predict_bench.py [--reps 5] [--out profiles/predict.md]
+
+`--components` measures the connected-component clean-up (evalpost.Components) instead, on the same batch: (c1) the fixed-logits
+post-processing with and without the spec, (c2) the whole `predict` call with and without it, (c3) the host route it replaces -
+masks="host", then scipy.ndimage.label per mask (tests/components_cases.py's labeller where scipy is missing) and numpy statistics -
+and the device time of the label + filter launches alone (events).  The threshold is the median probability of the batch, so the
+masks have structure (synthetic weights put every pixel above 0.35).
+
+    python tools/predict_bench.py --components [--keep largest] [--min-area 0] [--out profiles/components_bench.md]"""
 import argparse
 import io
 import os
@@ -65,11 +73,151 @@ def host_route(probs, invs, shapes, index, thr=THR):
     return out
 
 
+def host_components(masks, q16, keep, min_area, connectivity):
+    """the host route of the clean-up: label every mask, filter, statistics with numpy -> [(kept mask, area, box, q16 sum, n)]"""
+    try:
+        from scipy import ndimage
+        structure = ndimage.generate_binary_structure(2, 1 if connectivity == 4 else 2)
+    except ImportError:
+        ndimage = None
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import components_cases
+    out = []
+    for m, q in zip(masks, q16):
+        if ndimage is None:
+            lab = components_cases.label(m, connectivity)
+            ids, lab = np.unique(lab, return_inverse=True)                 # -1 (background) first, then ascending canonical labels
+            lab = lab.reshape(m.shape) + (0 if ids[0] == -1 else 1)
+            n = int(lab.max())
+        else:
+            lab, n = ndimage.label(m != 0, structure=structure)            # (labels ascend with the first pixel in raster order)
+        areas = np.bincount(lab.ravel(), minlength=n + 1)[1:]
+        ok = np.nonzero(areas >= min_area)[0]
+        if keep == "largest" and ok.size:
+            ok = ok[np.argmax(areas[ok])][None]                            # the first maximum: the lowest label
+        kept = np.isin(lab, ok + 1)
+        area = int(kept.sum())
+        ys, xs = np.nonzero(kept)
+        box = (int(xs.min()), int(ys.min()), int(xs.max()) + 1, int(ys.max()) + 1) if area else None
+        out.append((kept.astype(np.uint8) * 255, area, box, int(q[kept].sum()) if q is not None else 0, n))
+    return out, ndimage is not None
+
+
+def components_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs):
+    spec = evalpost.Components(a.keep, a.min_area, a.connectivity)
+    K = len(descs)
+    probs0 = evalpost.sigmoid_upsample(logits, SIZE, SIZE)
+    thr = float(probs0.median()) if a.thr is None else a.thr
+    ring, turn = [evalpost.EvalStaging(dev, mask_bytes=16) for _ in range(3)], [0]
+    scratch = {}
+
+    def post(with_spec, masks):
+        turn[0] = (turn[0] + 1) % 3
+        st = ring[turn[0]].pack_sizes(shapes, descs).upload()
+        table = evalpost.new_predict_stats(K, dev)
+        probs = evalpost.sigmoid_upsample(logits, SIZE, SIZE)
+        if not with_spec:
+            out = torch.empty(st.out_bytes, dtype=torch.uint8, device=dev) if masks else None
+            evalpost.predict_batch(probs, st, table, 0, thr, out_masks=out)
+            return st, None if out is None else out.cpu().numpy(), table.cpu().numpy(), None
+        if masks:
+            out = torch.empty(st.out_bytes, dtype=torch.uint8, device=dev)
+        else:
+            out = scratch["masks"] = scratch["masks"] if scratch.get("masks") is not None else torch.empty(st.out_bytes, dtype=torch.uint8, device=dev)
+        ktable, info = evalpost.new_predict_stats(K, dev), torch.zeros(K, 4, dtype=torch.int64, device=dev)
+        evalpost.predict_batch(probs, st, table, 0, thr, out_masks=out)
+        scratch["labels"] = evalpost.label_components(out, st, spec.connectivity, out=scratch.get("labels"))
+        scratch["work"] = evalpost.filter_work(st, dev, scratch.get("work"))
+        evalpost.filter_components(out, scratch["labels"], st, spec, info, 0, probs=probs, stats=ktable, work=scratch["work"])
+        return st, out.cpu().numpy() if masks else None, torch.cat([ktable, info], 1).cpu().numpy(), out
+
+    def unpack(st, buf):
+        return [buf[st.descs[k].out_off:st.descs[k].out_off + st.descs[k].pitch * st.descs[k].h_out].reshape(st.descs[k].h_out, st.descs[k].pitch)
+                [:, :st.descs[k].w_out] for k in range(K)]
+
+    q16 = [np.rint(evalpost.warp_to_original(probs0[k], invs[i], shapes[i]).cpu().numpy() * np.float32(65536)).astype(np.int64)
+           for k, i in enumerate(plan.index[:K])]
+
+    def host():
+        st, buf, stats, _ = post(False, True)
+        return host_components(unpack(st, buf), q16, spec.keep, spec.min_area, spec.connectivity)
+
+    (ref, used_scipy), (st, buf, rows, _) = host(), post(True, True)
+    same = True
+    for k, ((m, area, box, q, n), got) in enumerate(zip(ref, unpack(st, buf))):
+        r = [int(v) for v in rows[k]]
+        same &= bool(np.array_equal(got, m)) and r[0] == area and r[1] == q and (tuple(r[2:6]) == box if area else True) and r[6] == n and r[9] == 0
+
+    def device_only():
+        """label + filter alone on masks already on the device: events around the seven stream operations"""
+        st, _, _, out = post(True, False)
+        info, ktable = torch.zeros(K, 4, dtype=torch.int64, device=dev), evalpost.new_predict_stats(K, dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        fresh = evalpost.new_predict_stats(K, dev)
+        evalpost.predict_batch(probs0, st, fresh, 0, thr, out_masks=out)
+        e0.record()
+        labels = evalpost.label_components(out, st, spec.connectivity, out=scratch["labels"])
+        evalpost.filter_components(out, labels, st, spec, info, 0, probs=probs0, stats=ktable, work=scratch["work"])
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    pr = predict.Predictor(runner, pipe, thr=thr)
+    arms = [lambda: post(False, False), lambda: post(True, False), lambda: post(False, True), lambda: post(True, True), host,
+            lambda: pr.predict(files, exprs, images_per_batch=IMAGES, masks=None), lambda: pr.predict(files, exprs, images_per_batch=IMAGES, masks=None, components=spec),
+            lambda: pr.predict(files, exprs, images_per_batch=IMAGES, masks="host"), lambda: pr.predict(files, exprs, images_per_batch=IMAGES, masks="host", components=spec)]
+    for f in arms:
+        timed(f, 2)
+    t = [[] for _ in arms]
+    dev_ms = []
+    for _ in range(ROUNDS):
+        for f, acc in zip(arms, t):
+            acc.append(timed(f, a.reps) * 1e3)
+        dev_ms.append(statistics.median(device_only() for _ in range(a.reps)))
+
+    def row(name, v):
+        return "| %s | %s | %.3f | %.3f | %.3f ms |" % (name, " ".join("%.3f" % x for x in v), min(v), max(v), statistics.median(v))
+
+    ncomp, raw, keptarea = [int(v) for v in rows[:, 6]], [int(v) for v in rows[:, 8]], [int(v) for v in rows[:, 0]]
+    lines = ["# Connected-component clean-up of predicted masks: on the device against the host route", "",
+             "`python tools/predict_bench.py --components --keep %s --min-area %d --connectivity %d --reps %d` on %s: R50, %dx%d, synthetic"
+             % (spec.keep, spec.min_area, spec.connectivity, a.reps, torch.cuda.get_device_name(0), SIZE, SIZE),
+             "weights; %d synthetic 480x640 JPEGs x %d expressions = %d masks per call, thr %.4f (the batch's median probability unless --thr);"
+             % (IMAGES, EXPRS, K, thr),
+             "%d rounds with the arms interleaved, %d calls per round and arm; host clocks around work that ends with its results on the host,"
+             % (ROUNDS, a.reps), "except the device-time row (events around the memset and the six launches, masks resident).", "",
+             "| arm | rounds | min | max | median |", "|---|---|---|---|---|",
+             row("(c1) fixed logits, statistics only, no spec: `sigmoid_upsample` + pack + ONE `predict_batch` + table to the host, ms per %d masks" % K, t[0]),
+             row("(c1) the same with the spec: + `label_components` + `filter_components`, two more tables", t[1]),
+             row("(c1) fixed logits, masks to the host, no spec", t[2]),
+             row("(c1) the same with the spec (the FILTERED masks go to the host)", t[3]),
+             row("(c1) device time of label + filter alone (events)", dev_ms),
+             row("(c3) host route: masks to the host, %s per mask, numpy filter and statistics" % ("`scipy.ndimage.label`" if used_scipy else "the test oracle's labeller (no scipy here)"), t[4]),
+             row("(c2) whole `Predictor.predict`, masks=None, no spec, ms per call", t[5]),
+             row("(c2) whole `Predictor.predict`, masks=None, with the spec", t[6]),
+             row("(c2) whole `Predictor.predict`, masks=\"host\", no spec", t[7]),
+             row("(c2) whole `Predictor.predict`, masks=\"host\", with the spec", t[8]), "",
+             "Filtered masks, areas, boxes, score sums and component counts of the device and the host route equal: %s." % same,
+             "Components per mask before filtering: min %d, median %d, max %d; raw foreground min %d, max %d; kept min %d, max %d of %d pixels."
+             % (min(ncomp), statistics.median(ncomp), max(ncomp), min(raw), max(raw), min(keptarea), max(keptarea), shapes[0][0] * shapes[0][1]), ""]
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "predict.md"))
+    ap.add_argument("--out", default=None, help="default: profiles/predict.md, with --components profiles/components_bench.md")
+    ap.add_argument("--components", action="store_true", help="measure the connected-component clean-up instead")
+    ap.add_argument("--keep", choices=evalpost.Components.KEEP, default="largest")
+    ap.add_argument("--min-area", type=int, default=0)
+    ap.add_argument("--connectivity", type=int, choices=(4, 8), default=8)
+    ap.add_argument("--thr", type=float, default=None, help="--components only: the threshold (default: the batch's median probability)")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "components_bench.md" if a.components else "predict.md")
     if not torch.cuda.is_available():
         raise SystemExit("predict_bench needs a GPU (nothing here is measured on the CPU)")
     dev = torch.device("cuda:0")
@@ -90,6 +238,8 @@ def main():
     for _ in range(3):
         logits = runner.segment(img, word, plan.index).clone()
     descs = [(invs[i], i, k, row) for _, i, k, row in plan.descs]
+    if a.components:
+        return components_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
     ring, turn = [evalpost.EvalStaging(dev, mask_bytes=16) for _ in range(3)], [0]
     K = len(descs)
 
