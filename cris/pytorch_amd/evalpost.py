@@ -20,7 +20,11 @@ binary masks come out at the original sizes and (area, score, bounding box) accu
 `Components` is the optional mask clean-up between the launch that writes the masks and the numbers read from them:
 `label_components` (connected-component labels of the packed masks, three launches), `filter_components` (keep the largest
 component / drop the small ones in place, statistics over the kept pixels, three launches) and `mask_iou_batch` (intersection /
-union counts from mask bytes) - DESIGN.md 9b."""
+union counts from mask bytes) - DESIGN.md 9b.
+
+`rle_encode_batch` / `rle_collect` are the last stage of that chain: the packed masks, filtered or not, become COCO run-length
+encodings (rle.py) - the transition positions are found on the device (csrc/rle.hip, four launches), only they cross to the host,
+and the strings of a batch are built there in one vectorised pass."""
 import ctypes as C
 
 import numpy as np
@@ -380,6 +384,69 @@ def check_component_info(info):
     if bad.size:
         raise RuntimeError("connected components: the union-find walk of row(s) %s hit its iteration cap (corrupt label buffer?)" % bad[:8].tolist())
     return info
+
+
+RLE_RB, RLE_CG = 32, 64  # rows of a band / columns of a block in csrc/rle.hip (the shapes at which its kernels change path)
+
+
+def rle_work(descs, device, out=None):
+    """the scratch of `rle_encode_batch` for this batch (per-segment counts, one base per descriptor): `out` when it is large
+    enough, a new int64 buffer otherwise.  Nothing has to be zeroed."""
+    words = (hip.load().cris_rle_work_bytes(C.addressof(descs.descs), descs.n) + 7) // 8
+    if out is not None and out.numel() >= words:
+        return out
+    return torch.empty(words + words // 4, dtype=torch.int64, device=device)
+
+
+def rle_pixels(descs):
+    """sum of h * w over the descriptors: the run words that always suffice (a checkerboard has one transition per pixel)"""
+    return sum(descs.descs[i].h_out * descs.descs[i].w_out for i in range(descs.n))
+
+
+def rle_encode_batch(masks_u8, descs, runs=None, work=None):
+    """COCO run-length encoding of every descriptor's mask in the packed buffer `masks_u8` (what iou_batch / predict_batch wrote
+    into out_masks, filtered or not; `descs`: the uploaded EvalStaging of that launch) -> (runs, totals): runs, uint32 positions
+    as an int32 buffer, receives the column-major transition positions (rle.py: P) of descriptor 0, then 1, ..., packed and
+    ascending within each; totals, int64 [n + 1]: the number of positions per descriptor and, last, their sum.  runs: a
+    contiguous int32 buffer to reuse, of ANY size - the launch never writes past it, positions that do not fit are dropped and
+    totals[n] still tells the words needed (`rle_collect` then grows and encodes again); None allocates one word per pixel,
+    which always suffices.  work: scratch from `rle_work` to reuse.  Four launches on the current stream (cris_rle_encode), none
+    depending on the content; nothing is synchronised or read here."""
+    _check_packed("rle_encode_batch", masks_u8, descs)
+    if descs.n < 1:
+        raise ValueError("rle_encode_batch: no descriptors")
+    if runs is None:
+        runs = torch.empty(max(rle_pixels(descs), 1), dtype=torch.int32, device=masks_u8.device)
+    elif runs.dtype != torch.int32 or runs.dim() != 1 or not runs.is_contiguous() or runs.numel() < 1 or runs.device != masks_u8.device:
+        raise ValueError("rle_encode_batch: runs must be a contiguous int32 buffer on the masks' device")
+    work = rle_work(descs, masks_u8.device, work)
+    totals = torch.empty(descs.n + 1, dtype=torch.int64, device=masks_u8.device)
+    hip.call("cris_rle_encode", ptr(masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n, ptr(work),
+             8 * work.numel(), ptr(runs), runs.numel(), ptr(totals), _stream())
+    return runs, totals
+
+
+def rle_collect(runs, totals, descs, masks_u8=None, work=None):
+    """The read of `rle_encode_batch`: totals first, then exactly totals[n] words of `runs` - two device-to-host copies - and the
+    strings of the whole batch in one vectorised pass on the host (rle.strings_from_positions) -> list of {"size": [h, w],
+    "counts": bytes} per descriptor.  When totals[n] exceeds the capacity of `runs`, a buffer of totals[n] words is allocated and
+    the batch is encoded once more from `masks_u8` (the buffer the first call read, still unchanged; without it the overflow is
+    a RuntimeError)."""
+    from . import rle
+    n = descs.n
+    t = totals.cpu().numpy()
+    need = int(t[n])
+    if t.shape != (n + 1,) or need != int(t[:n].sum()) or need < 0:
+        raise RuntimeError("rle_collect: totals %r do not belong to these %d descriptors" % (t.tolist()[:8], n))
+    if need > runs.numel():
+        if masks_u8 is None:
+            raise RuntimeError("rle_collect: the batch needs %d run words, the buffer holds %d; pass masks_u8 to encode again" % (need, runs.numel()))
+        runs, totals = rle_encode_batch(masks_u8, descs, runs=torch.empty(need, dtype=torch.int32, device=runs.device), work=work)
+        t = totals.cpu().numpy()
+        if int(t[n]) != need:
+            raise RuntimeError("rle_collect: the masks changed between the two encodes (%d positions, then %d)" % (need, int(t[n])))
+    words = runs[:need].cpu().numpy().view(np.uint32)
+    return rle.strings_from_positions(words, t[:n], [(descs.descs[i].h_out, descs.descs[i].w_out) for i in range(n)])
 
 
 def mask_iou_batch(pred_masks_u8, descs, gt_masks_u8, counts, row0):

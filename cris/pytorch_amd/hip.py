@@ -362,6 +362,8 @@ _SIGS = {
     "cris_filter_components_work_bytes": (C.c_size_t, [C.c_size_t, I]),
     "cris_filter_components": (I, [P, C.c_size_t, P, C.c_size_t, P, P, I, I, I, P, C.c_size_t, P, I, P, I, I, I, F, P, I, P]),
     "cris_mask_iou_batch": (I, [P, C.c_size_t, P, P, I, P, C.c_size_t, P, I, P]),
+    "cris_rle_work_bytes": (C.c_size_t, [P, I]),
+    "cris_rle_encode": (I, [P, C.c_size_t, P, P, I, P, C.c_size_t, P, C.c_size_t, P, P]),
     "cris_preprocess_batch": (I, [P, I, I, I, P, P, P, P, P, P, P, P]),
     "cris_gray_sum_batch": (I, [P, P, I, P, P]),
     "cris_preprocess_batch_aug": (I, [P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),

@@ -17,18 +17,24 @@ up; the table of the whole call comes back once at the end, the masks once per b
 (connected components: DESIGN.md 9b): the masks of a batch stay in a device buffer, `evalpost.label_components` and
 `evalpost.filter_components` run on the stream, and the call returns ComponentPrediction - area, box and score of the KEPT pixels.
 
+`masks="rle"` ends that chain on the device too: the masks of a batch stay in an internal device buffer, `evalpost.rle_encode_batch`
+finds their run-length transitions (csrc/rle.hip) and `Prediction.mask` is the COCO RLE dict of rle.py - a few hundred bytes per
+mask cross to the host instead of the image-sized mask.  `coco_results` turns such a result into the list a results file holds.
+
     python -m cris.pytorch_amd.predict --weights CKPT --config YAML --image F --expr "the left one" --out-prefix P [--keep largest]
+                                       [--rle-json RESULTS.json]
 """
 from collections import namedtuple
 
 import numpy as np
 import torch
 
-from . import evalpost
+from . import evalpost, rle
 
 Prediction = namedtuple("Prediction", "sentence mask area box score")
-Prediction.__doc__ = """sentence: the expression; mask: uint8 [h, w] of 0 / 255 at the image's own size (numpy array, CUDA tensor view or
-None: `masks`); area: pixels above the threshold; box: (x0, y0, x1, y1) half-open, None when area == 0; score: the mean warped
+Prediction.__doc__ = """sentence: the expression; mask: uint8 [h, w] of 0 / 255 at the image's own size (numpy array, CUDA tensor view, None
+or with masks="rle" the COCO RLE dict {"size": [h, w], "counts": bytes} of that mask: `masks`); area: pixels above the threshold;
+box: (x0, y0, x1, y1) half-open, None when area == 0; score: the mean warped
 probability over those pixels, score_q16 / (65536 * area) in float64 (each pixel's value rounded to 1 / 65536), 0.0 when area == 0"""
 
 ComponentPrediction = namedtuple("ComponentPrediction", "sentence mask area box score n_components raw_area")
@@ -41,7 +47,7 @@ BatchPlan.__doc__ = """images lo .. lo + n of the call; image_index: the batch's
 one; index: image (within the batch) of every expression, padded to a multiple of `multiple` by repeating the last one; descs:
 (inverse or None, image within the batch, probability map, statistics row of the WHOLE call) per real expression"""
 
-MASK_MODES = ("host", "device", None)
+MASK_MODES = ("host", "device", "rle", None)
 
 
 def _pad_to(n, multiple):
@@ -83,7 +89,7 @@ def _check_components(value, default):
 def _check_inputs(images, expressions, images_per_batch, masks):
     """-> (kind 'bytes' / 'array', expressions as lists); everything here is host-only"""
     if masks not in MASK_MODES:
-        raise ValueError("predict: masks must be 'host', 'device' or None, got %r" % (masks,))
+        raise ValueError("predict: masks must be 'host', 'device', 'rle' or None, got %r" % (masks,))
     if int(images_per_batch) < 1:
         raise ValueError("predict: images_per_batch must be positive")
     images, expressions = list(images), list(expressions)
@@ -130,6 +136,7 @@ class Predictor:
         self._segment = getattr(model, "segment", None) or getattr(model, "segment_expressions", None)
         self._ring, self._turn = None, 0
         self._cc_masks = self._cc_labels = self._cc_work = None       # component clean-up scratch, reused across batches
+        self._rle_runs = self._rle_work = None                        # run-length encoder buffers, reused across batches
 
     def _staging(self):
         if self._ring is None:          # (the first device allocation: after every argument check)
@@ -137,13 +144,26 @@ class Predictor:
         self._turn = (self._turn + 1) % self.RING
         return self._ring[self._turn]
 
+    def _mask_buffer(self, st):
+        """the internal mask buffer of a batch whose masks never leave the device as bytes"""
+        if self._cc_masks is None or self._cc_masks.numel() < st.out_bytes:
+            self._cc_masks = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.uint8, device=self.device)
+        return self._cc_masks
+
+    def _encode_rle(self, st, out):
+        """the batch's masks in `out` as RLE dicts: the encoder on the stream, then the batch's read (totals, then the positions).
+        The run buffer holds one word per mask byte, which no mask can exceed, so nothing is ever encoded twice."""
+        if self._rle_runs is None or self._rle_runs.numel() < st.out_bytes:
+            self._rle_runs = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.int32, device=self.device)
+        self._rle_work = evalpost.rle_work(st, self.device, self._rle_work)
+        runs, totals = evalpost.rle_encode_batch(out, st, runs=self._rle_runs, work=self._rle_work)
+        return evalpost.rle_collect(runs, totals, st, masks_u8=out, work=self._rle_work)
+
     def _component_buffers(self, st, out):
         """the mask buffer of a batch that is cleaned up (out=None: an internal one that never leaves the device) and the label /
         work scratch, grown when a batch needs more and reused otherwise"""
         if out is None:
-            if self._cc_masks is None or self._cc_masks.numel() < st.out_bytes:
-                self._cc_masks = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.uint8, device=self.device)
-            out = self._cc_masks
+            out = self._mask_buffer(st)
         if self._cc_labels is None or self._cc_labels.numel() < st.out_bytes:
             self._cc_labels = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.int32, device=self.device)
         self._cc_work = evalpost.filter_work(st, self.device, self._cc_work)
@@ -153,8 +173,10 @@ class Predictor:
     def predict(self, images, expressions, images_per_batch=8, masks="host", components="default"):
         """images: JPEG bytes per image, or uint8 RGB [h, w, 3] arrays / tensors per image (one kind per call; JPEG files come
         back turned by their EXIF orientation, as cv2.imdecode returns them).  expressions: per image a str or a non-empty list
-        of str.  masks: "host" (numpy arrays, one device-to-host copy per batch), "device" (views of one CUDA buffer per batch)
-        or None (statistics only: no mask buffer is allocated).  Returns a list per image of Prediction per expression.
+        of str.  masks: "host" (numpy arrays, one device-to-host copy per batch), "device" (views of one CUDA buffer per batch),
+        "rle" (COCO run-length dicts, rle.py: the masks stay in an internal device buffer, are encoded there after any clean-up,
+        and only the run positions are copied) or None (statistics only: no mask buffer is allocated).  Returns a list per image
+        of Prediction per expression.
         components: an evalpost.Components, None (no clean-up) or "default" (the constructor's).  With a spec every mask is
         labelled and filtered on the device before anything is read, the statistics are those of the kept pixels and the entries
         are ComponentPrediction; with masks=None the masks live in an internal device buffer and never reach the host."""
@@ -187,7 +209,10 @@ class Predictor:
             else:
                 logits = self.model(img[torch.tensor(b.index, device=self.device)], word)
             probs = evalpost.sigmoid_upsample(logits, img.shape[-2], img.shape[-1])
-            out = None if masks is None else torch.empty(st.out_bytes, dtype=torch.uint8, device=self.device)
+            as_rle = masks == "rle"
+            out = None if masks is None or as_rle else torch.empty(st.out_bytes, dtype=torch.uint8, device=self.device)
+            if as_rle and spec is None:
+                out = self._mask_buffer(st)
             if spec is not None:
                 out = self._component_buffers(st, out)
             evalpost.predict_batch(probs, st, table, 0, self.thr, out_masks=out)
@@ -196,6 +221,9 @@ class Predictor:
                 evalpost.filter_components(out, labels, st, spec, info, 0, probs=probs, stats=ktable, work=self._cc_work)
             if masks is None:
                 kept += [None] * K
+                continue
+            if as_rle:
+                kept += self._encode_rle(st, out)
                 continue
             buf = out.cpu().numpy() if masks == "host" else out        # the batch's masks: one copy
             for k in range(K):
@@ -232,6 +260,28 @@ class Predictor:
                 k += 1
             result.append(row)
         return result
+
+
+def coco_results(out, image_ids, expressions=True):
+    """The entries of a COCO-style results file from what `predict(..., masks="rle")` returned: out[i][j] belongs to image_ids[i].
+    Per expression {"image_id", "sentence" (left out with expressions=False), "segmentation": the RLE with str counts (goes
+    straight into json.dump), "bbox": [x, y, w, h] (COCO's form of Prediction.box; zeros for an empty mask), "area", "score"}.
+    Host only."""
+    out, image_ids = list(out), list(image_ids)
+    if len(out) != len(image_ids):
+        raise ValueError("coco_results: %d images but %d image ids" % (len(out), len(image_ids)))
+    entries = []
+    for image_id, preds in zip(image_ids, out):
+        for p in preds:
+            if not isinstance(p.mask, dict):
+                raise ValueError("coco_results needs a result of predict(..., masks='rle'), got a mask of type %s" % type(p.mask).__name__)
+            x0, y0, x1, y1 = p.box if p.box is not None else (0, 0, 0, 0)
+            entry = {"image_id": image_id, "sentence": p.sentence, "segmentation": rle.to_json(p.mask),
+                     "bbox": [int(x0), int(y0), int(x1 - x0), int(y1 - y0)], "area": int(p.area), "score": float(p.score)}
+            if not expressions:
+                del entry["sentence"]
+            entries.append(entry)
+    return entries
 
 
 class _WordHashTokenizer:
@@ -275,7 +325,10 @@ def main(argv=None):
     ap.add_argument("--config", help="the yaml the model was trained with (not needed with --synthetic)")
     ap.add_argument("--image", required=True, help="a JPEG file, or any image file Pillow opens")
     ap.add_argument("--expr", action="append", required=True, help="a referring expression; repeat for several")
-    ap.add_argument("--out-prefix", required=True)
+    ap.add_argument("--out-prefix", help="write PREFIX_<j>.png per expression (required unless --rle-json is given)")
+    ap.add_argument("--rle-json", metavar="PATH", help="write the COCO-style results list (RLE segmentation, bbox, area, score per "
+                    "expression) to PATH; the masks are encoded on the GPU")
+    ap.add_argument("--image-id", default=None, help="the image_id of the --rle-json entries (default: the image's file name)")
     ap.add_argument("--thr", type=float, default=0.35)
     ap.add_argument("--synthetic", nargs="?", const="r50", default=None, metavar="SPEC",
                     help="arch.synthetic_state_dict of r50 (default), r101 or tiny instead of --weights / --config")
@@ -289,6 +342,8 @@ def main(argv=None):
         spec = evalpost.Components(a.keep, a.min_area, a.connectivity)
     except ValueError as e:
         ap.error(str(e))
+    if not a.out_prefix and not a.rle_json:
+        ap.error("one of --out-prefix and --rle-json is required")
     if not torch.cuda.is_available():
         raise SystemExit("predict needs a GPU (there is no CPU fallback)")
     dev = torch.device("cuda:0")
@@ -314,7 +369,17 @@ def main(argv=None):
     with open(a.image, "rb") as f:
         data = f.read()
     image = data if data[:2] == b"\xff\xd8" else np.array(Image.open(a.image).convert("RGB"))
-    out = Predictor(runner, pipe, thr=a.thr, components=spec).predict([image], [a.expr], images_per_batch=1, masks="host")[0]
+    predictor = Predictor(runner, pipe, thr=a.thr, components=spec)
+    if a.rle_json:
+        import json
+        encoded = predictor.predict([image], [a.expr], images_per_batch=1, masks="rle")
+        os.makedirs(os.path.dirname(os.path.abspath(a.rle_json)), exist_ok=True)
+        with open(a.rle_json, "w") as f:
+            json.dump(coco_results(encoded, [a.image_id if a.image_id is not None else os.path.basename(a.image)]), f)
+        print("%s\t%d expressions\t%d bytes of RLE" % (a.rle_json, len(encoded[0]), sum(len(p.mask["counts"]) for p in encoded[0])))
+        if not a.out_prefix:
+            return encoded[0]
+    out = predictor.predict([image], [a.expr], images_per_batch=1, masks="host")[0]
     os.makedirs(os.path.dirname(os.path.abspath(a.out_prefix)), exist_ok=True)
     for j, p in enumerate(out):
         path = "%s_%d.png" % (a.out_prefix, j)

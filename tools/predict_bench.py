@@ -17,7 +17,14 @@ masks="host", then scipy.ndimage.label per mask (tests/components_cases.py's lab
 and the device time of the label + filter launches alone (events).  The threshold is the median probability of the batch, so the
 masks have structure (synthetic weights put every pixel above 0.35).
 
-    python tools/predict_bench.py --components [--keep largest] [--min-area 0] [--out profiles/components_bench.md]"""
+    python tools/predict_bench.py --components [--keep largest] [--min-area 0] [--out profiles/components_bench.md]
+
+`--rle` measures the COCO run-length output (masks="rle": csrc/rle.hip, rle.py) on the same batch and threshold rule: the whole
+`predict` call with masks=None, masks="host", masks="host" followed by `rle.encode` per mask on the host (the route the mode
+replaces) and masks="rle"; the encoder and its read alone on resident masks; numpy's encode alone; the device time of the four
+launches (events); the bytes each arm copies to the host and the run counts of the batch.
+
+    python tools/predict_bench.py --rle [--out profiles/rle.md]"""
 import argparse
 import io
 import os
@@ -207,17 +214,100 @@ def components_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, pla
         f.write(text)
 
 
+def rle_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs):
+    from cris.pytorch_amd import rle
+    K = len(descs)
+    probs0 = evalpost.sigmoid_upsample(logits, SIZE, SIZE)
+    thr = float(probs0.median()) if a.thr is None else a.thr
+    pr = predict.Predictor(runner, pipe, thr=thr)
+
+    def call(masks):
+        return [p for x in pr.predict(files, exprs, images_per_batch=IMAGES, masks=masks) for p in x]
+
+    def host_encode():
+        return [rle.encode(p.mask) for p in call("host")]
+
+    # the batch's masks resident on the device, for the encoder alone
+    st = evalpost.EvalStaging(dev, mask_bytes=16).pack_sizes(shapes, descs).upload()
+    out = torch.empty(st.out_bytes, dtype=torch.uint8, device=dev)
+    evalpost.predict_batch(probs0, st, evalpost.new_predict_stats(K, dev), 0, thr, out_masks=out)
+    runs = torch.empty(st.out_bytes, dtype=torch.int32, device=dev)
+    work = evalpost.rle_work(st, dev)
+    host_masks = [p.mask for p in call("host")]
+
+    def device_only():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        evalpost.rle_encode_batch(out, st, runs=runs, work=work)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def encode_and_collect():
+        return evalpost.rle_collect(*evalpost.rle_encode_batch(out, st, runs=runs, work=work), st)
+
+    def numpy_only():
+        return [rle.encode(m) for m in host_masks]
+
+    totals = evalpost.rle_encode_batch(out, st, runs=runs, work=work)[1].cpu().numpy()
+    same = [p.mask for p in call("rle")] == host_encode() == encode_and_collect()
+    arms = [lambda: call(None), lambda: call("host"), host_encode, lambda: call("rle"), encode_and_collect, numpy_only]
+    for f in arms:
+        timed(f, 2)
+    t = [[] for _ in arms]
+    dev_ms = []
+    for _ in range(ROUNDS):
+        for f, acc in zip(arms, t):
+            acc.append(timed(f, a.reps) * 1e3)
+        dev_ms.append(statistics.median(device_only() for _ in range(a.reps)))
+
+    def row(name, v, note=""):
+        return "| %s | %s | %.3f | %.3f | %.3f ms | %s |" % (name, " ".join("%.3f" % x for x in v), min(v), max(v), statistics.median(v), note)
+
+    table = K * 6 * 8
+    rle_bytes = (K + 1) * 8 + 4 * int(totals[K]) + table
+    strings = sum(len(r["counts"]) for r in encode_and_collect())
+    spread = max(t[2]) - min(t[2])
+    slower = statistics.median(t[3]) - statistics.median(t[2])
+    lines = ["# COCO run-length masks from predict: encoded on the device against numpy on the host", "",
+             "`python tools/predict_bench.py --rle --reps %d` on %s: R50, %dx%d, synthetic weights; %d synthetic 480x640 JPEGs x %d"
+             % (a.reps, torch.cuda.get_device_name(0), SIZE, SIZE, IMAGES, EXPRS),
+             "expressions = %d masks per call, thr %.4f (the batch's median probability unless --thr); %d rounds with the arms interleaved,"
+             % (K, thr, ROUNDS),
+             "%d calls per round and arm; host clocks around work that ends with its results on the host, except the device-time row"
+             % a.reps, "(events around the four launches of `rle_encode_batch`, masks resident).", "",
+             "| arm | rounds | min | max | median | bytes to the host per call |", "|---|---|---|---|---|---|",
+             row("whole `Predictor.predict`, masks=None, ms per call", t[0], "%d (the table)" % table),
+             row("whole `Predictor.predict`, masks=\"host\"", t[1], "%d (the masks) + %d" % (st.out_bytes, table)),
+             row("whole `Predictor.predict`, masks=\"host\", then `rle.encode` per mask on the host (the route replaced)", t[2], "%d + %d" % (st.out_bytes, table)),
+             row("whole `Predictor.predict`, masks=\"rle\"", t[3], "%d (totals and positions) + %d" % (rle_bytes - table, table)),
+             row("masks resident: `rle_encode_batch` + `rle_collect` (launches, two copies, strings), ms per %d masks" % K, t[4], "%d" % (rle_bytes - table)),
+             row("masks on the host: `rle.encode` per mask (numpy), ms per %d masks" % K, t[5], "-"),
+             row("device time of `rle_encode_batch` alone (events)", dev_ms, "-"), "",
+             "The three routes give equal RLE dicts: %s.  Transition positions per mask: min %d, median %d, max %d; %d in the batch; the"
+             % (same, int(totals[:K].min()), int(statistics.median(int(v) for v in totals[:K])), int(totals[:K].max()), int(totals[K])),
+             "compressed strings of the batch hold %d bytes against %d bytes of masks." % (strings, st.out_bytes), "",
+             "masks=\"rle\" against the host-encode arm: median %+.3f ms; spread of the host-encode arm over its rounds %.3f ms."
+             % (slower, spread), ""]
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None, help="default: profiles/predict.md, with --components profiles/components_bench.md")
+    ap.add_argument("--out", default=None, help="default: profiles/predict.md, with --components profiles/components_bench.md, with --rle profiles/rle.md")
+    ap.add_argument("--rle", action="store_true", help="measure the run-length mask output instead")
     ap.add_argument("--components", action="store_true", help="measure the connected-component clean-up instead")
     ap.add_argument("--keep", choices=evalpost.Components.KEEP, default="largest")
     ap.add_argument("--min-area", type=int, default=0)
     ap.add_argument("--connectivity", type=int, choices=(4, 8), default=8)
-    ap.add_argument("--thr", type=float, default=None, help="--components only: the threshold (default: the batch's median probability)")
+    ap.add_argument("--thr", type=float, default=None, help="--components / --rle only: the threshold (default: the batch's median probability)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "components_bench.md" if a.components else "predict.md")
+    a.out = a.out or os.path.join(ROOT, "profiles", "components_bench.md" if a.components else "rle.md" if a.rle else "predict.md")
     if not torch.cuda.is_available():
         raise SystemExit("predict_bench needs a GPU (nothing here is measured on the CPU)")
     dev = torch.device("cuda:0")
@@ -240,6 +330,8 @@ def main():
     descs = [(invs[i], i, k, row) for _, i, k, row in plan.descs]
     if a.components:
         return components_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
+    if a.rle:
+        return rle_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
     ring, turn = [evalpost.EvalStaging(dev, mask_bytes=16) for _ in range(3)], [0]
     K = len(descs)
 
