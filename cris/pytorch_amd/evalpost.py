@@ -24,8 +24,14 @@ union counts from mask bytes) - DESIGN.md 9b.
 
 `rle_encode_batch` / `rle_collect` are the last stage of that chain: the packed masks, filtered or not, become COCO run-length
 encodings (rle.py) - the transition positions are found on the device (csrc/rle.hip, four launches), only they cross to the host,
-and the strings of a batch are built there in one vectorised pass."""
+and the strings of a batch are built there in one vectorised pass.
+
+`Boundary` is the optional second figure of an evaluation pass, Boundary IoU (Cheng et al., CVPR 2021): IoU restricted to the pixels
+within `radius` of each mask's contour.  `erode_batch` (erosion of the packed masks by a square, or the boundary it leaves) and
+`boundary_iou_batch` (intersection / union counts of the prediction's and the ground truth's boundaries) are three launches each of
+csrc/morph.hip over 64-bit bit planes of the masks - DESIGN.md 9b."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -460,3 +466,123 @@ def mask_iou_batch(pred_masks_u8, descs, gt_masks_u8, counts, row0):
         raise ValueError("mask_iou_batch: counts must be contiguous int32 [R, 2] and row0 inside it")
     hip.call("cris_mask_iou_batch", ptr(pred_masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n,
              ptr(gt_masks_u8), gt_masks_u8.numel(), counts.data_ptr() + 8 * int(row0), counts.shape[0] - int(row0), _stream())
+
+
+class Boundary:
+    """Boundary IoU as a validated value (the style of `Components`): the boundary of an h x w mask is what an erosion by a
+    (2 d + 1)-square removes from it, d = max(int(round(ratio * sqrt(h^2 + w^2))), min_radius) - Python's round, half to even, in
+    float64; ratio=0.02 is the figure LVIS and the COCO panoptic tooling use.  Host only."""
+
+    __slots__ = ("ratio", "min_radius")
+
+    def __init__(self, ratio=0.02, min_radius=1):
+        if isinstance(ratio, bool) or not isinstance(ratio, (int, float, np.integer, np.floating)) or not (math.isfinite(ratio) and 0 < ratio <= 1):
+            raise ValueError("Boundary: ratio must be a finite number in (0, 1], got %r" % (ratio,))
+        if isinstance(min_radius, bool) or not isinstance(min_radius, (int, np.integer)) or min_radius < 1:
+            raise ValueError("Boundary: min_radius must be an integer >= 1, got %r" % (min_radius,))
+        object.__setattr__(self, "ratio", float(ratio))
+        object.__setattr__(self, "min_radius", int(min_radius))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Boundary is immutable")
+
+    def radius(self, h, w):
+        """the erosion radius of an h x w mask"""
+        h, w = int(h), int(w)
+        if h < 1 or w < 1:
+            raise ValueError("Boundary.radius: the size must be positive, got %r x %r" % (h, w))
+        return max(int(round(self.ratio * math.sqrt(h * h + w * w))), self.min_radius)
+
+    def __eq__(self, other):
+        return isinstance(other, Boundary) and (self.ratio, self.min_radius) == (other.ratio, other.min_radius)
+
+    def __hash__(self):
+        return hash((self.ratio, self.min_radius))
+
+    def __repr__(self):
+        return "Boundary(ratio=%r, min_radius=%d)" % (self.ratio, self.min_radius)
+
+
+def boundary_spec(value, what="boundary"):
+    """None, True or a Boundary -> the spec to apply (True: Boundary()) or None; anything else is a ValueError.  Host only: callers
+    run this before they touch a device."""
+    if value is None:
+        return None
+    if value is True:
+        return Boundary()
+    if not isinstance(value, Boundary):
+        raise ValueError("%s must be None, True or an evalpost.Boundary, got %r" % (what, value))
+    return value
+
+
+def boundary_radii(descs, spec):
+    """the radius of every descriptor of `descs` (an EvalStaging) under `spec`, from its output size -> host int32 [n]"""
+    if not isinstance(spec, Boundary):
+        raise ValueError("boundary_radii: spec must be an evalpost.Boundary, got %r" % (spec,))
+    return np.array([spec.radius(descs.descs[i].h_out, descs.descs[i].w_out) for i in range(descs.n)], dtype=np.int32)
+
+
+def boundary_work(descs, device, out=None):
+    """the scratch of `erode_batch` / `boundary_iou_batch` for this batch (four bit planes): `out` when it is large enough, a new
+    int64 buffer otherwise.  Nothing has to be zeroed."""
+    words = (hip.load().cris_boundary_work_bytes(C.addressof(descs.descs), descs.n) + 7) // 8
+    if out is not None and out.numel() >= words:
+        return out
+    return torch.empty(max(words + words // 4, 1), dtype=torch.int64, device=device)
+
+
+def _radii(name, radii, descs, device):
+    """(host int32 [n], device int32 [n]) of `radii`: a host sequence is uploaded with one small asynchronous copy, a CUDA int32
+    tensor is read back for the library's host check (callers on the hot path pass the host sequence)"""
+    if torch.is_tensor(radii) and radii.device.type == "cuda":
+        if radii.dtype != torch.int32 or radii.dim() != 1 or not radii.is_contiguous() or radii.numel() != descs.n:
+            raise ValueError("%s: radii must be a contiguous int32 tensor of one radius per descriptor" % name)
+        return np.ascontiguousarray(radii.cpu().numpy()), radii
+    given = np.asarray(radii.numpy() if torch.is_tensor(radii) else radii)
+    if given.ndim != 1 or given.shape[0] != descs.n or given.dtype.kind not in "iu":
+        raise ValueError("%s: radii must be one integer radius per descriptor (%d), got %r" % (name, descs.n, radii))
+    if (given < 1).any() or (given > 2 ** 31 - 1).any():
+        raise ValueError("%s: every radius must be in 1 .. 2^31 - 1" % name)
+    host = np.ascontiguousarray(given.astype(np.int32))
+    pinned = torch.from_numpy(host.copy()).pin_memory()
+    return host, pinned.to(device, non_blocking=True)
+
+
+def erode_batch(masks_u8, descs, radii, out=None, boundary=False, work=None):
+    """Erosion of every descriptor's mask in the packed buffer `masks_u8` by the (2 r + 1)-square, r = radii[i] (`boundary_radii`;
+    a host sequence or a CUDA int32 tensor) -> a packed uint8 buffer with the same layout: 255 where the whole window lies inside
+    the image and is foreground (byte != 0, x < w_out), else 0; boundary=True: 255 where the mask is foreground and the erosion is
+    not.  Only the h_out x w_out pixels of every descriptor are written - pitch padding, gaps and tail of `out` keep their bytes
+    (a new buffer is zeroed).  out: a uint8 buffer of at least descs.out_bytes to reuse; `masks_u8` itself erodes in place.  work:
+    scratch from `boundary_work`.  Three launches on the current stream (cris_erode_masks), none depending on the content."""
+    _check_packed("erode_batch", masks_u8, descs)
+    if descs.n < 1:
+        raise ValueError("erode_batch: no descriptors")
+    if out is None:
+        out = torch.zeros(descs.out_bytes, dtype=torch.uint8, device=masks_u8.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < descs.out_bytes or out.device != masks_u8.device:
+        raise ValueError("erode_batch: out must be a contiguous uint8 buffer of at least descs.out_bytes on the masks' device")
+    host, dev = _radii("erode_batch", radii, descs, masks_u8.device)
+    work = boundary_work(descs, masks_u8.device, work)
+    hip.call("cris_erode_masks", ptr(masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n,
+             host.ctypes.data_as(C.c_void_p), ptr(dev), ptr(work), 8 * work.numel(), ptr(out), out.numel(), 1 if boundary else 0, _stream())
+    return out
+
+
+def boundary_iou_batch(pred_masks_u8, descs, gt_masks_u8, radii, counts, row0, work=None):
+    """counts[row0 + row] += (#(B(pred) and B(gt)), #(B(pred) or B(gt))) per descriptor, B(M) = M & ~erode(M, radii[i]) the
+    boundary of width radii[i] (cris_boundary_iou_batch): pred in the packed output layout (out_off), gt the staging's packed masks
+    (mask_off).  counts: [R, 2] cuda int32 like `mask_iou_batch`'s; radii: `boundary_radii` (a host sequence or a CUDA int32
+    tensor); work: scratch from `boundary_work`.  Three launches on the current stream, none depending on the content."""
+    _check_packed("boundary_iou_batch", pred_masks_u8, descs)
+    if descs.n < 1:
+        raise ValueError("boundary_iou_batch: no descriptors")
+    if gt_masks_u8.dtype != torch.uint8 or not gt_masks_u8.is_contiguous() or gt_masks_u8.device != pred_masks_u8.device:
+        raise ValueError("boundary_iou_batch: gt_masks_u8 must be a contiguous uint8 buffer on the masks' device")
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != 2 or not counts.is_contiguous() or not 0 <= row0 < counts.shape[0]:
+        raise ValueError("boundary_iou_batch: counts must be contiguous int32 [R, 2] and row0 inside it")
+    host, dev = _radii("boundary_iou_batch", radii, descs, pred_masks_u8.device)
+    work = boundary_work(descs, pred_masks_u8.device, work)
+    hip.call("cris_boundary_iou_batch", ptr(pred_masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n,
+             ptr(gt_masks_u8), gt_masks_u8.numel(), host.ctypes.data_as(C.c_void_p), ptr(dev), ptr(work), 8 * work.numel(),
+             counts.data_ptr() + 8 * int(row0), counts.shape[0] - int(row0), _stream())

@@ -17,6 +17,11 @@ the table into a `SweepResult` - IoU, overall IoU and Pr@X per threshold, the be
 `validate` / `inference` take `components=evalpost.Components(...)`: every predicted mask is cleaned up on the device (connected
 components) before it is counted - `iou_batch` writes the masks, `label_components` / `filter_components` rewrite them
 in place and `evalpost.mask_iou_batch` adds the counts of the filtered masks to the pass's table.
+
+`validate` / `inference` take `boundary=True` or `evalpost.Boundary(...)`: next to the mask figures the pass counts Boundary IoU
+(Cheng et al., CVPR 2021) - the masks the batch wrote (filtered when `components` is given) and the ground truth are eroded on the
+device and `evalpost.boundary_iou_batch` adds (intersection, union) of the two boundaries to a second table, read with the first;
+`boundary_counts`, `boundary_per_sample`, `boundary_iou` and `boundary_prec` hold the result (`metrics` of that table).
 """
 import math
 
@@ -174,6 +179,8 @@ class Evaluator:
         self._turn = 0
         self.per_sample = self.counts = self.sweep_counts = self.component_info = None
         self._cc_masks = self._cc_labels = self._cc_work = self._cc_counts = None      # component clean-up scratch, reused across batches
+        self.boundary_counts = self.boundary_per_sample = self.boundary_iou = self.boundary_prec = None
+        self._bd_masks = self._bd_work = None                      # boundary scratch (the batch's masks, the bit planes), likewise
 
     def _staging(self):
         self._turn = (self._turn + 1) % self.RING
@@ -205,6 +212,28 @@ class Evaluator:
         evalpost.mask_iou_batch(out, st, st.masks, table, row0)
         return out
 
+    def _boundary_masks(self, st):
+        """the internal, reused buffer a batch's masks are written to when only the boundary counts need them"""
+        if self._bd_masks is None or self._bd_masks.numel() < st.out_bytes:
+            self._bd_masks = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.uint8, device=self.device)
+        return self._bd_masks
+
+    def _boundary_counts(self, bspec, masks, st, btable, row0):
+        """one batch with a Boundary spec: `masks` (what the batch wrote, filtered or not) against the staging's ground truth"""
+        self._bd_work = evalpost.boundary_work(st, self.device, self._bd_work)
+        evalpost.boundary_iou_batch(masks, st, st.masks, evalpost.boundary_radii(st, bspec), btable, row0, work=self._bd_work)
+
+    def _finish_boundary(self, btable, n, group, gather):
+        """the pass's read of the boundary table (None: a pass without the spec), after the counts'"""
+        self.boundary_counts = self.boundary_per_sample = self.boundary_iou = self.boundary_prec = None
+        if btable is None:
+            return
+        counts = btable[:n].cpu()
+        if gather:
+            counts = gather_counts(counts, group)
+        self.boundary_counts = counts.numpy()
+        self.boundary_iou, self.boundary_prec, self.boundary_per_sample = metrics(self.boundary_counts)
+
     def _finish_components(self, info, n):
         """the pass's read of the component table (after the counts'): raises when an error column is set"""
         self.component_info = evalpost.check_component_info(info[:n].cpu().numpy())
@@ -217,10 +246,13 @@ class Evaluator:
         return iou, prec
 
     @torch.no_grad()
-    def validate(self, records, indices=None, batch_size=32, group=None, components=None):
+    def validate(self, records, indices=None, batch_size=32, group=None, components=None, boundary=None):
         """components: None or an evalpost.Components - clean every predicted mask up before it is counted (`component_info`
-        then holds the [n, 4] table of evalpost.INFO_FIELDS per sample)"""
+        then holds the [n, 4] table of evalpost.INFO_FIELDS per sample).  boundary: None, True or an evalpost.Boundary - also
+        count Boundary IoU of the (cleaned) masks: `boundary_iou`, `boundary_prec`, `boundary_per_sample`, `boundary_counts`;
+        the return value stays (iou, prec) of the masks."""
         spec = evalpost.components_spec(components, "validate: components")
+        bspec = evalpost.boundary_spec(boundary, "validate: boundary")
         if self.pipe.mode != "val":
             raise ValueError("validate needs a RecordPipeline in mode 'val'")
         indices = list(range(len(records))) if indices is None else [int(i) for i in indices]
@@ -228,6 +260,7 @@ class Evaluator:
             raise ValueError("validate: no records")
         table = torch.zeros(len(indices), 2, dtype=torch.int32, device=self.device)
         info = None if spec is None else torch.zeros(len(indices), 4, dtype=torch.int64, device=self.device)
+        btable = None if bspec is None else torch.zeros(len(indices), 2, dtype=torch.int32, device=self.device)
         for lo in range(0, len(indices), batch_size):
             recs = [records[i] for i in indices[lo:lo + batch_size]]
             img, word, params = self.pipe(recs)
@@ -238,18 +271,24 @@ class Evaluator:
             st = self._staging().pack(*plan_validate(self._masks(recs, params), [p["inverse"] for p in params])).upload()
             probs = evalpost.sigmoid_upsample(self.model(img, word), img.shape[-2], img.shape[-1])
             if spec is None:
-                evalpost.iou_batch(probs, st, st.masks, table, lo, self.thr)
+                out = None if bspec is None else self._boundary_masks(st)
+                evalpost.iou_batch(probs, st, st.masks, table, lo, self.thr, out_masks=out)
             else:
-                self._clean_counts(spec, probs, st, table, lo, info)
+                out = self._clean_counts(spec, probs, st, table, lo, info)
+            if bspec is not None:
+                self._boundary_counts(bspec, out, st, btable, lo)
         result = self._finish(table, len(indices), group)
+        self._finish_boundary(btable, len(indices), group, True)
         if spec is not None:
             self._finish_components(info, len(indices))
         return result
 
     @torch.no_grad()
-    def inference(self, records, indices=None, images_per_batch=8, visualize=None, components=None):
-        """components: as for `validate`; a `visualize` callback then receives the FILTERED masks and their IoUs"""
+    def inference(self, records, indices=None, images_per_batch=8, visualize=None, components=None, boundary=None):
+        """components: as for `validate`; a `visualize` callback then receives the FILTERED masks and their IoUs.  boundary: as for
+        `validate` (the expressions of one image share its ground truth)"""
         spec = evalpost.components_spec(components, "inference: components")
+        bspec = evalpost.boundary_spec(boundary, "inference: boundary")
         if self.pipe.mode != "test":
             raise ValueError("inference needs a RecordPipeline in mode 'test'")
         indices = list(range(len(records))) if indices is None else [int(i) for i in indices]
@@ -259,6 +298,7 @@ class Evaluator:
         total = sum(len(r["sents"]) for b in batches for r in b)
         table = torch.zeros(total, 2, dtype=torch.int32, device=self.device)
         info = None if spec is None else torch.zeros(total, 4, dtype=torch.int64, device=self.device)
+        btable = None if bspec is None else torch.zeros(total, 2, dtype=torch.int32, device=self.device)
         row0 = 0
         for recs in batches:
             img, params = self.pipe(recs)
@@ -280,13 +320,18 @@ class Evaluator:
             probs = evalpost.sigmoid_upsample(logits, img.shape[-2], img.shape[-1])
             out = None if visualize is None else torch.empty(st.out_bytes, dtype=torch.uint8, device=self.device)
             if spec is None:
+                if out is None and bspec is not None:
+                    out = self._boundary_masks(st)
                 evalpost.iou_batch(probs, st, st.masks, table, row0, self.thr, out_masks=out)
             else:
                 out = self._clean_counts(spec, probs, st, table, row0, info, out)
+            if bspec is not None:
+                self._boundary_counts(bspec, out, st, btable, row0)
             if visualize is not None:
                 self._visualize(visualize, recs, sents, index, st, table[row0:row0 + K].cpu().numpy(), out.cpu().numpy())
             row0 += K
         result = self._finish(table, total, None)
+        self._finish_boundary(btable, total, None, False)
         if spec is not None:
             self._finish_components(info, total)
         return result

@@ -364,6 +364,9 @@ _SIGS = {
     "cris_mask_iou_batch": (I, [P, C.c_size_t, P, P, I, P, C.c_size_t, P, I, P]),
     "cris_rle_work_bytes": (C.c_size_t, [P, I]),
     "cris_rle_encode": (I, [P, C.c_size_t, P, P, I, P, C.c_size_t, P, C.c_size_t, P, P]),
+    "cris_boundary_work_bytes": (C.c_size_t, [P, I]),
+    "cris_erode_masks": (I, [P, C.c_size_t, P, P, I, P, P, P, C.c_size_t, P, C.c_size_t, I, P]),
+    "cris_boundary_iou_batch": (I, [P, C.c_size_t, P, P, I, P, C.c_size_t, P, P, P, C.c_size_t, P, I, P]),
     "cris_preprocess_batch": (I, [P, I, I, I, P, P, P, P, P, P, P, P]),
     "cris_gray_sum_batch": (I, [P, P, I, P, P]),
     "cris_preprocess_batch_aug": (I, [P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),

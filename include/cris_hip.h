@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_rle_encode / cris_rle_work_bytes (COCO run-length encoding of the packed masks on the device) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/rle.hip), every other launcher keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_rle_encode / cris_rle_work_bytes (COCO run-length encoding of the packed masks on the device) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/rle.hip), every other launcher keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_erode_masks / cris_boundary_iou_batch / cris_boundary_work_bytes (square-structuring-element erosion of the packed masks and the Boundary IoU counts built on it) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/morph.hip), the radii travel as a separate int32 array, every other launcher keeps its signature, its kernel and its results, and a binding that knows the three binds them at load, so a library without them is refused there */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -603,6 +603,33 @@ int cris_mask_iou_batch(const unsigned char* pred, size_t pred_bytes, const cris
 size_t cris_rle_work_bytes(const cris_eval_desc* descs_host, int n);
 int cris_rle_encode(const unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev, int n,
                     void* work, size_t work_bytes, unsigned* runs, size_t run_words, long long* totals, void* stream);
+/* Erosion by a (2 r + 1)-square of the same packed masks and the Boundary IoU counts built on it (csrc/morph.hip; DESIGN.md 9b).
+ * Foreground as above: byte != 0 and x < w_out, the pitch padding is never read as a pixel; outside the image is background.  With
+ * r = radii[i] >= 1 the radius of descriptor i (computed on the host: the device reads integers; radii_host is checked here,
+ * radii_dev - the same n values in device memory - is read by the kernels),
+ *     E_r(M)[y, x] = 1 iff every pixel of [y - r, y + r] x [x - r, x + r] lies inside the image and is foreground
+ * (r iterations of a 3 x 3 erosion behind a one-pixel zero border), empty when 2 r + 1 > min(h_out, w_out), and B_r(M) = M & ~E_r(M).
+ * cris_erode_masks reads `masks` at out_off / pitch and writes bytes 0 / 255 at the same offsets of `out`: E_r (boundary = 0) or
+ * B_r (boundary = 1); no byte outside a descriptor's h_out x w_out pixels is written (not the pitch padding, not the gaps, not the
+ * tail).  out == masks (in place) is allowed: every source byte is read by the first launch, every output byte written by the third.
+ * cris_boundary_iou_batch: counts[d.row] += (|B_r(P) & B_r(G)|, |B_r(P) | B_r(G)|), P at d.out_off of `pred`, G at d.mask_off of `gt`,
+ * both with d.pitch; the int32 [count_rows][2] table of cris_eval_iou_batch.  work: device scratch of
+ * cris_boundary_work_bytes(descs_host, n) bytes = 4 bit planes (prediction, ground truth, each raw and eroded along x) of n slots of
+ * max over the batch of h_out * ceil(w_out / 64) 64-bit words (cris_erode_masks uses two of the four and accepts half; 0 for NULL
+ * descriptors or n outside 1 .. 65535); nothing has to be zeroed.  Three launches each on the stream (pack to bit planes by wave
+ * ballot, window AND along x, window AND along y + counts or bytes), none depending on the content; integers only, the counts by one
+ * integer atomic pair per block after a reduction: the same numbers on every run.  Checked on the host before the first launch:
+ * operands non-NULL, n in 1 .. 65535, boundary, alignment (work 8-byte; radii_dev, counts 4-byte), every radius >= 1, work_bytes, and
+ * per descriptor h_out, w_out >= 1, h_out * w_out < 2^31, w_out <= pitch, pitch a multiple of 4, pitch * h_out < 2^31, out_off >= 0
+ * and the rectangle inside mask_bytes and out_bytes (pred_bytes), mask_off >= 0 and the rectangle inside gt_bytes, row < count_rows
+ * (map is ignored). */
+size_t cris_boundary_work_bytes(const cris_eval_desc* descs_host, int n);
+int cris_erode_masks(const unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev, int n,
+                     const int* radii_host, const int* radii_dev, void* work, size_t work_bytes, unsigned char* out, size_t out_bytes,
+                     int boundary, void* stream);
+int cris_boundary_iou_batch(const unsigned char* pred, size_t pred_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev,
+                            int n, const unsigned char* gt, size_t gt_bytes, const int* radii_host, const int* radii_dev, void* work,
+                            size_t work_bytes, int* counts, int count_rows, void* stream);
 /* ---- input preprocessing (reference utils/dataset.py:146-168 RefDataset.__getitem__, :207-221 convert; csrc/inputpipe.hip) ----
  * One launch per batch: img_out[b] = ((cv2.warpAffine(rgb_u8, mat, (S_w, S_h), INTER_CUBIC, borderValue=border_rgb).float()
  * / 255 - mean) / std) as [3][S_h][S_w] (through lut_img [3][256]), mask_out[b] = cv2.warpAffine(mask_u8, mat, ...,

@@ -10,7 +10,11 @@ The forward alone (graph replay on a resident batch) is timed for scale.  Writes
     python tools/eval_bench.py [--records 256] [--out profiles/eval_throughput.md]
 
 `--sweep [T]` measures the threshold sweep instead (sweep_main: one `iou_sweep_batch` launch against T `iou_batch` launches, a
-whole `Evaluator.sweep` pass against a whole `validate` pass) and writes profiles/eval_sweep.md."""
+whole `Evaluator.sweep` pass against a whole `validate` pass) and writes profiles/eval_sweep.md.
+
+`--boundary` measures Boundary IoU instead (boundary_main: the three launches of `boundary_iou_batch` next to the `iou_batch`
+launch that writes the masks, the host route they replace - scipy.ndimage.binary_erosion per mask - and a whole `validate` pass
+with and without the spec) and writes profiles/boundary_iou.md."""
 import argparse
 import io
 import os
@@ -177,15 +181,148 @@ def sweep_main(a, dev, recs, pipe, runner):
         f.write(text)
 
 
+def boundary_main(a, dev, recs, pipe, runner):
+    """--boundary: on the fixed probabilities of one batch of 32 (descriptors and masks uploaded once), launches only: (a) one
+    `iou_batch` that also writes the masks; (b) `boundary_iou_batch` on those masks (three launches); (c) `erode_batch` (three
+    launches, bytes out).  (d) the host route on the same masks: scipy's binary_erosion of prediction and ground truth per sample
+    and numpy counts.  Then (e) a whole `Evaluator.validate` pass without and with the spec, interleaved."""
+    spec = evalpost.Boundary()
+    img, word, params = pipe(recs[:BATCH])
+    for _ in range(3):
+        logits = runner(img, word).clone()
+    masks_u8 = [pngdec.decode_gray(r["mask"]) for r in recs[:BATCH]]
+    st = evalpost.EvalStaging(dev).pack(*evaluate.plan_validate(masks_u8, [p["inverse"] for p in params])).upload()
+    probs = evalpost.sigmoid_upsample(logits, SIZE, SIZE)
+    one = torch.zeros(BATCH, 2, dtype=torch.int32, device=dev)
+    btab = torch.zeros(BATCH, 2, dtype=torch.int32, device=dev)
+    out = torch.zeros(st.out_bytes, dtype=torch.uint8, device=dev)
+    eroded = torch.zeros(st.out_bytes, dtype=torch.uint8, device=dev)
+    work = evalpost.boundary_work(st, dev)
+    radii_host = evalpost.boundary_radii(st, spec)
+    radii = torch.from_numpy(radii_host).to(dev)
+    evalpost.iou_batch(probs, st, st.masks, one, 0, 0.35, out_masks=out)
+    # the synthetic weights predict little: count the ground truth against a shifted copy of itself as well, so that both
+    # boundaries are there (the launches do the same work whatever the masks hold; the host route does not)
+    shifted = torch.zeros_like(out)
+    for i in range(st.n):
+        d = st.descs[i]
+        g = st.masks[d.mask_off:d.mask_off + d.pitch * d.h_out].view(d.h_out, d.pitch)
+        shifted[d.out_off:d.out_off + d.pitch * d.h_out].view(d.h_out, d.pitch)[7:, 5:d.w_out] = g[:-7, :d.w_out - 5]
+
+    def arm_a():
+        evalpost.iou_batch(probs, st, st.masks, one, 0, 0.35, out_masks=out)
+
+    def arm_b():
+        evalpost.boundary_iou_batch(shifted, st, st.masks, radii, btab, 0, work=work)
+
+    def arm_c():
+        evalpost.erode_batch(shifted, st, radii, out=eroded, work=work)
+
+    def host_counts():
+        from scipy import ndimage
+        square = np.ones((3, 3), bool)
+        res = []
+        for i in range(st.n):
+            d = st.descs[i]
+            p = pred_host[d.out_off:d.out_off + d.pitch * d.h_out].reshape(d.h_out, d.pitch)[:, :d.w_out] != 0
+            g = masks_u8[i].numpy() != 0
+            r = int(radii_host[i])
+            bp = p & ~ndimage.binary_erosion(p, structure=square, iterations=r, border_value=0)
+            bg = g & ~ndimage.binary_erosion(g, structure=square, iterations=r, border_value=0)
+            res.append([int((bp & bg).sum()), int((bp | bg).sum())])
+        return res
+
+    btab.zero_()
+    arm_b()
+    got = btab.cpu().numpy().tolist()
+    pred_host = shifted.cpu().numpy()
+    try:
+        want = host_counts()
+        t_host = []
+        for _ in range(ROUNDS):
+            t0 = time.perf_counter()
+            host_counts()
+            t_host.append((time.perf_counter() - t0) * 1e3)
+    except ImportError:
+        want = t_host = None
+    arms = (arm_a, arm_b, arm_c)
+    calls = 200 * a.reps                                           # a timed window is >= 0.1 s of device work
+    for f in arms:
+        timed(f, 2)
+    t_arm = [[] for _ in arms]
+    for _ in range(ROUNDS):
+        for f, v in zip(arms, t_arm):
+            one.zero_()
+            btab.zero_()                                           # (the launches accumulate: keep the int32 counts far from 2^31)
+            v.append(timed(f, calls) * 1e3)
+    t_a, t_b, t_c = t_arm
+
+    ev = evaluate.Evaluator(runner, pipe)
+    ev.validate(recs[:2 * BATCH], batch_size=BATCH)                # warm-up: eager call, graph capture
+    ev.validate(recs[:2 * BATCH], batch_size=BATCH, boundary=spec)
+    p_plain, p_bd = [], []
+    for _ in range(ROUNDS):
+        t0 = time.perf_counter()
+        ev.validate(recs, batch_size=BATCH)
+        torch.cuda.synchronize()
+        p_plain.append(len(recs) / (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        ev.validate(recs, batch_size=BATCH, boundary=spec)
+        torch.cuda.synchronize()
+        p_bd.append(len(recs) / (time.perf_counter() - t0))
+
+    def row(name, v, unit):
+        if v is None:
+            return "| %s | not measured (scipy is not installed) | | | |" % name
+        return "| %s | %s | %.3f | %.3f | %.3f %s |" % (name, " ".join("%.3f" % x for x in v), min(v), max(v), statistics.median(v), unit)
+
+    med = statistics.median
+    pixels = sum(int(m.shape[0]) * int(m.shape[1]) for m in masks_u8)
+    lines = ["# Boundary IoU: three launches on bit planes against per-mask erosion on the host", "",
+             "`python tools/eval_bench.py --boundary --records %d --reps %d` on %s: R50, %dx%d, %d tokens, synthetic weights, HIP-graph"
+             % (a.records, a.reps, torch.cuda.get_device_name(0), SIZE, SIZE, WORD_LEN),
+             "replay; %d synthetic records (originals 416-544 x 576-704), batch %d, radii %d .. %d (2 %% of the diagonal), %d rounds with"
+             % (a.records, BATCH, int(radii_host.min()), int(radii_host.max()), ROUNDS),
+             "the arms interleaved.  Arms (a)-(c) are launches only, on the resident descriptors and masks of one batch of %d (%d"
+             % (BATCH, pixels),
+             "original-size pixels; the prediction is the ground truth shifted by (7, 5), so both boundaries exist); each figure is the mean",
+             "of %d back-to-back calls inside a host clock that ends in a device synchronisation.  (d) is host work on the same masks,"
+             % calls,
+             "already in host memory (no copy is counted).  (e) is a whole pass (JPEG decode, letter-box, forward, post-processing, one host",
+             "read), the two arms alternating in one process.", "",
+             "| arm | rounds | min | max | median |", "|---|---|---|---|---|",
+             row("(a) one `iou_batch` launch that writes the masks, ms", t_a, "ms"),
+             row("(b) `boundary_iou_batch`, three launches, ms", t_b, "ms"),
+             row("(c) `erode_batch`, three launches, ms", t_c, "ms"),
+             row("(d) host route: 2 x 32 `scipy.ndimage.binary_erosion` + numpy counts, ms", t_host, "ms"),
+             row("(e) whole `Evaluator.validate` pass, samples/s", p_plain, "samples/s"),
+             row("(e) whole `Evaluator.validate` pass with `boundary=True`, samples/s", p_bd, "samples/s"), "",
+             "* (b) / (a) = %.2f." % (med(t_b) / med(t_a)),
+             "* pass with the spec / pass without = %.3f in samples/s (per round %s)."
+             % (med(p_bd) / med(p_plain), " ".join("%.3f" % (x / y) for x, y in zip(p_bd, p_plain)))]
+    if t_host is not None:
+        lines += ["* (d) / (b) = %.0f." % (med(t_host) / med(t_b)),
+                  "* The device counts of the batch equal the host route's: %s." % (got == want)]
+    lines += ["* Last pass with the spec: mask IoU %.4f, boundary IoU %.4f." % (float(np.mean(ev.per_sample)), ev.boundary_iou), ""]
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sweep", type=int, nargs="?", const=19, default=None, metavar="T",
                     help="measure the threshold sweep at T thresholds (default 19) instead; writes profiles/eval_sweep.md")
+    ap.add_argument("--boundary", action="store_true", help="measure Boundary IoU instead; writes profiles/boundary_iou.md")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "eval_throughput.md" if a.sweep is None else "eval_sweep.md")
+    if a.boundary and a.sweep is not None:
+        raise SystemExit("--boundary and --sweep are separate measurements")
+    a.out = a.out or os.path.join(ROOT, "profiles", "boundary_iou.md" if a.boundary else "eval_throughput.md" if a.sweep is None else "eval_sweep.md")
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU (nothing here is measured on the CPU)")
     dev = torch.device("cuda:0")
@@ -196,6 +333,8 @@ def main():
     runner = InferenceRunner(clip, head, arch.synthetic_state_dict(clip, head, 0), dev)
     if a.sweep is not None:
         return sweep_main(a, dev, recs, pipe, runner)
+    if a.boundary:
+        return boundary_main(a, dev, recs, pipe, runner)
 
     # ---- (a) post-processing of one batch of 32 on fixed logits
     img, word, params = pipe(recs[:BATCH])
