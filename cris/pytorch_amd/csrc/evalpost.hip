@@ -600,8 +600,10 @@ __device__ __forceinline__ bool cc_union(int* L, int a, int b, int cap) {
 // Launch 1.  Visibility: the kernel boundary - a block reads mask bytes the previous launch wrote and writes label words no other
 // block of this launch touches; the union-find runs in LDS (workgroup-scope atomics between the barriers).
 // blockIdx.y = descriptor, blockIdx.x strides over its 32 x 32 tiles (tiles cover the pitch: padding words are written -1).
+// bg = 1 labels the BACKGROUND instead (cris_fill_holes): the pixels whose byte is 0, x < w_out; everything after this line of the
+// three launches sees label words only.
 __global__ __launch_bounds__(256) void cc_tile_label_kernel(const unsigned char* __restrict__ masks, const cris_eval_desc* __restrict__ descs,
-                                                            int conn8, int* __restrict__ labels) {
+                                                            int conn8, int bg, int* __restrict__ labels) {
     __shared__ int lab[CC_TILE * CC_TILE];
     const cris_eval_desc d = descs[blockIdx.y];
     const int tiles_x = (d.pitch + CC_TILE - 1) / CC_TILE, tiles_y = (d.h_out + CC_TILE - 1) / CC_TILE;
@@ -616,7 +618,7 @@ __global__ __launch_bounds__(256) void cc_tile_label_kernel(const unsigned char*
         bool fg[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            fg[j] = in && x0 + j < d.w_out && ((mword >> (8 * j)) & 0xffu) != 0u;
+            fg[j] = in && x0 + j < d.w_out && (((mword >> (8 * j)) & 0xffu) != 0u) != (bg != 0);
             lab[l0 + j] = fg[j] ? l0 + j : -1;
         }
         __syncthreads();
@@ -717,6 +719,22 @@ __device__ __forceinline__ int cc_block_sum(int v, int* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// A[lab] += cnt for every lane with lab >= 0, pre-summed over the wave: the lanes that hold one label add once.  Called by all 64
+// lanes (wave-uniform control flow around it); each pass retires its leader's label: at most 64 passes.
+__device__ __forceinline__ void cc_wave_add(int* A, int lab, int cnt, int lane) {
+    unsigned long long todo = __ballot(lab >= 0);
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int lv = __shfl(lab, leader, 64);
+        const bool m = lab == lv;
+        int s = m ? cnt : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == leader) atomicAdd(A + lv, s);
+        todo &= ~__ballot(m);
+    }
+}
+
 // Launch 4.  Visibility: the kernel boundary (labels are final; areas / info only receive integer atomicAdd / atomicOr, exact and
 // order-free).  areas[out_off + root] += 1 per pixel, pre-summed per wave: the lanes that hold one label add once (a wave's 256
 // consecutive pixels mostly share it).  info[row] = (n_components, kept_components, raw_area, error): [2] += foreground pixels,
@@ -750,19 +768,7 @@ __global__ __launch_bounds__(256) void cc_count_kernel(const cris_eval_desc* __r
         for (int j = 1; j < 4; ++j)                                // equal neighbours of a thread's four pixels: one count
             if (lab[j] >= 0 && lab[j] == lab[j - 1]) { cnt[j] += cnt[j - 1]; lab[j - 1] = -1; }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            unsigned long long todo = __ballot(lab[j] >= 0);
-            while (todo) {                                         // each pass retires its leader: at most 64 passes
-                const int leader = __ffsll((long long)todo) - 1;
-                const int lv = __shfl(lab[j], leader, 64);
-                const bool m = lab[j] == lv;
-                int s = m ? cnt[j] : 0;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-                if (lane == leader) atomicAdd(A + lv, s);
-                todo &= ~__ballot(m);
-            }
-        }
+        for (int j = 0; j < 4; ++j) cc_wave_add(A, lab[j], cnt[j], lane);
     }
     const int raws = cc_block_sum(raw, red[0]), bads = cc_block_sum(bad, red[1]);
     if (threadIdx.x == 0) {
@@ -931,6 +937,22 @@ static const char* cc_check_descs(const cris_eval_desc* descs_host, int n, size_
     return nullptr;
 }
 
+// launches 1 - 3 for checked operands: the components of the foreground (bg = 0) or of the background (bg = 1)
+static int cc_label_launches(const unsigned char* masks, const cris_eval_desc* descs_dev, int n, int conn8, int bg, long most,
+                             int* labels, void* stream) {
+    const int cap = 2048 / n > 8 ? 2048 / n : 8;                   // the grid of cris_eval_iou_batch
+    const long tiles = (most * 4 + CC_TILE * CC_TILE - 1) / (CC_TILE * CC_TILE) + 1;      // (a bound: the blocks stride over their own count)
+    hipLaunchKernelGGL(cc_tile_label_kernel, dim3(cris_grid_1d(tiles, 1, 4 * cap), n), dim3(256), 0, (hipStream_t)stream, masks, descs_dev,
+                       conn8, bg, labels);
+    CRIS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cc_merge_borders_kernel, dim3(cris_grid_1d(tiles, 1, 4 * cap), n), dim3(64), 0, (hipStream_t)stream, descs_dev, conn8,
+                       labels);
+    CRIS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cc_flatten_kernel, dim3(cris_grid_1d(most, 256, cap), n), dim3(256), 0, (hipStream_t)stream, descs_dev, labels);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int cris_label_components(const unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host,
                                      const cris_eval_desc* descs_dev, int n, int connectivity, int* labels, size_t label_words,
                                      void* stream) {
@@ -942,18 +964,7 @@ extern "C" int cris_label_components(const unsigned char* masks, size_t mask_byt
     long most = 0;
     const char* bad = cc_check_descs(descs_host, n, mask_bytes, -1, false, 0, &most);
     CRIS_CHECK_ARG(!bad, bad);
-    const int cap = 2048 / n > 8 ? 2048 / n : 8;                   // the grid of cris_eval_iou_batch
-    const int conn8 = connectivity == 8;
-    const long tiles = (most * 4 + CC_TILE * CC_TILE - 1) / (CC_TILE * CC_TILE) + 1;      // (a bound: the blocks stride over their own count)
-    hipLaunchKernelGGL(cc_tile_label_kernel, dim3(cris_grid_1d(tiles, 1, 4 * cap), n), dim3(256), 0, (hipStream_t)stream, masks, descs_dev,
-                       conn8, labels);
-    CRIS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cc_merge_borders_kernel, dim3(cris_grid_1d(tiles, 1, 4 * cap), n), dim3(64), 0, (hipStream_t)stream, descs_dev, conn8,
-                       labels);
-    CRIS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cc_flatten_kernel, dim3(cris_grid_1d(most, 256, cap), n), dim3(256), 0, (hipStream_t)stream, descs_dev, labels);
-    CRIS_LAUNCH_CHECK();
-    return 0;
+    return cc_label_launches(masks, descs_dev, n, connectivity == 8, 0, most, labels, stream);
 }
 
 extern "C" size_t cris_filter_components_work_bytes(size_t mask_bytes, int n) {
@@ -1019,6 +1030,134 @@ extern "C" int cris_mask_iou_batch(const unsigned char* pred, size_t pred_bytes,
     const int cap = 2048 / n > 8 ? 2048 / n : 8;                   // the grid of cris_eval_iou_batch
     hipLaunchKernelGGL(mask_iou_batch_kernel, dim3(cris_grid_1d(most, 256, cap), n), dim3(256), 0, (hipStream_t)stream, pred, descs_dev, gt,
                        counts);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- hole filling: the components of the BACKGROUND that own no pixel of the image's outer frame ----
+//   cris_fill_holes   1 - 3  the labeller's launches with bg = 1: the label word of a background pixel is its component's root
+//                     (the work buffer is zeroed by a memset node on the stream)
+//                     4 cc_hole_count   area per root (bits 0 .. 30 of its word) and CC_FRAME when the component owns a frame pixel
+//                     5 cc_hole_fill    the pixels of unmarked roots of area <= max_area become 255
+#define CC_FRAME 0x80000000u
+
+// Launch 4.  Visibility: the kernel boundary (labels are final).  areas[out_off + root] receives integer atomicAdd (the wave's
+// pre-summed count, as in cc_count_kernel) and atomicOr of bit 31, which no area reaches (pitch * h_out < 2^31): exact, order-free.
+// info[row][3] |= 1 when a pixel carries CC_ERR or a label outside the rectangle (such a word indexes nothing, here or in launch 5).
+__global__ __launch_bounds__(256) void cc_hole_count_kernel(const cris_eval_desc* __restrict__ descs, const int* __restrict__ labels,
+                                                            int* __restrict__ areas, unsigned long long* __restrict__ info) {
+    __shared__ int red[4];
+    const cris_eval_desc d = descs[blockIdx.y];
+    const int* __restrict__ L = labels + d.out_off;
+    int* A = areas + d.out_off;
+    const int gpr = d.pitch >> 2, lane = threadIdx.x & 63, limit = d.pitch * d.h_out;
+    const long total = (long)gpr * d.h_out;
+    int bad = 0;
+    for (long base = (long)blockIdx.x * blockDim.x; base < total; base += (long)gridDim.x * blockDim.x) {      // (uniform trip count)
+        const long g = base + threadIdx.x;
+        int lab[4] = {-1, -1, -1, -1}, cnt[4] = {1, 1, 1, 1};
+        if (g < total) {
+            const int y = (int)(g / gpr), x0 = (int)(g % gpr) * 4;
+            const int4 v = *reinterpret_cast<const int4*>(L + (size_t)y * d.pitch + x0);
+            const int* vv = reinterpret_cast<const int*>(&v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x = x0 + j;
+                if (x >= d.w_out) continue;
+                const bool wild = vv[j] < -1 || vv[j] >= limit;
+                lab[j] = wild ? -1 : vv[j];
+                bad |= wild ? 1 : 0;
+                if (lab[j] >= 0 && (y == 0 || y == d.h_out - 1 || x == 0 || x == d.w_out - 1))
+                    atomicOr(reinterpret_cast<unsigned int*>(A) + lab[j], CC_FRAME);
+            }
+        }
+#pragma unroll
+        for (int j = 1; j < 4; ++j)                                // equal neighbours of a thread's four pixels: one count
+            if (lab[j] >= 0 && lab[j] == lab[j - 1]) { cnt[j] += cnt[j - 1]; lab[j - 1] = -1; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cc_wave_add(A, lab[j], cnt[j], lane);
+    }
+    const int bads = cc_block_sum(bad, red);
+    if (threadIdx.x == 0 && bads) atomicOr(info + 4 * (size_t)d.row + 3, 1ull);
+}
+
+// Launch 5.  Visibility: the kernel boundary (areas and marks are complete; a block rewrites mask words no other block touches, and
+// only the bytes of filled pixels change: a byte that was 0 becomes 255, the other bytes of its word are stored as they were read).
+// info[row] += (holes filled, pixels filled, holes of any area, 0): a hole is counted at its root, the pixel whose label is its own index.
+__global__ __launch_bounds__(256) void cc_hole_fill_kernel(const cris_eval_desc* __restrict__ descs, const int* __restrict__ labels,
+                                                           const int* __restrict__ areas, int max_area, unsigned char* __restrict__ masks,
+                                                           unsigned long long* __restrict__ info) {
+    __shared__ int red[3][4];
+    const cris_eval_desc d = descs[blockIdx.y];
+    const int* __restrict__ L = labels + d.out_off;
+    const int* __restrict__ A = areas + d.out_off;
+    const int gpr = d.pitch >> 2, limit = d.pitch * d.h_out;
+    const long total = (long)gpr * d.h_out;
+    int holes = 0, filled = 0, pixels = 0;
+    for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long)gridDim.x * blockDim.x) {
+        const int y = (int)(g / gpr), x0 = (int)(g % gpr) * 4;
+        const int i0 = y * d.pitch + x0;
+        const int4 v = *reinterpret_cast<const int4*>(L + i0);
+        const int* vv = reinterpret_cast<const int*>(&v);
+        unsigned int oword = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int lab = vv[j];
+            if (x0 + j >= d.w_out || lab < 0 || lab >= limit) continue;
+            const unsigned int a = (unsigned int)A[lab];
+            if (a & CC_FRAME) continue;                            // joined to the outside: no hole
+            const int root = lab == i0 + j ? 1 : 0;
+            holes += root;
+            if (max_area >= 0 && a > (unsigned int)max_area) continue;
+            oword |= 0xffu << (8 * j);
+            pixels += 1;
+            filled += root;
+        }
+        if (oword) {
+            unsigned int* p = reinterpret_cast<unsigned int*>(masks + d.out_off + (size_t)y * d.pitch + x0);
+            *p |= oword;
+        }
+    }
+    const int fs = cc_block_sum(filled, red[0]), ps = cc_block_sum(pixels, red[1]), hs = cc_block_sum(holes, red[2]);
+    if (threadIdx.x == 0) {
+        if (fs) atomicAdd(info + 4 * (size_t)d.row, (unsigned long long)fs);
+        if (ps) atomicAdd(info + 4 * (size_t)d.row + 1, (unsigned long long)ps);
+        if (hs) atomicAdd(info + 4 * (size_t)d.row + 2, (unsigned long long)hs);
+    }
+}
+
+extern "C" size_t cris_fill_holes_work_bytes(size_t mask_bytes) { return (mask_bytes * 4 + 7) & ~(size_t)7; }
+
+extern "C" int cris_fill_holes(unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev, int n,
+                               int connectivity, int max_area, int* labels, size_t label_words, void* work, size_t work_bytes,
+                               long long* info, int info_rows, void* stream) {
+    CRIS_CHECK_ARG(masks && descs_host && descs_dev && labels && work && info, "null operand");
+    CRIS_CHECK_ARG(n > 0 && n <= 65535, "n must be in 1 .. 65535");
+    CRIS_CHECK_ARG(connectivity == 4 || connectivity == 8, "connectivity must be 4 or 8");
+    CRIS_CHECK_ARG(max_area >= -1, "max_area must be >= 0, or -1 for no cap");
+    CRIS_CHECK_ARG(info_rows > 0, "bad sizes");
+    CRIS_CHECK_ARG(((uintptr_t)masks & 3) == 0 && ((uintptr_t)labels & 15) == 0 && ((uintptr_t)work & 15) == 0 && ((uintptr_t)info & 7) == 0,
+                   "masks must be 4-byte, labels and work 16-byte, info 8-byte aligned");
+    CRIS_CHECK_ARG(label_words >= mask_bytes, "the label buffer must hold one word per mask byte");
+    CRIS_CHECK_ARG(work_bytes >= cris_fill_holes_work_bytes(mask_bytes), "the work buffer is too small");
+    long most = 0;
+    const char* bad = cc_check_descs(descs_host, n, mask_bytes, info_rows, false, 0, &most);
+    CRIS_CHECK_ARG(!bad, bad);
+    const int rc = cc_label_launches(masks, descs_dev, n, connectivity == 8, 1, most, labels, stream);
+    if (rc) return rc;
+    const hipError_t e = hipMemsetAsync(work, 0, cris_fill_holes_work_bytes(mask_bytes), (hipStream_t)stream);
+    if (e != hipSuccess) {
+        cris_set_error("%s: memset failed: %s", __func__, hipGetErrorString(e));
+        return (int)e;
+    }
+    int* areas = reinterpret_cast<int*>(work);
+    unsigned long long* inf = reinterpret_cast<unsigned long long*>(info);
+    const int cap = 2048 / n > 8 ? 2048 / n : 8;                   // the grid of cris_eval_iou_batch
+    const dim3 grid(cris_grid_1d(most, 256, cap), n);
+    hipLaunchKernelGGL(cc_hole_count_kernel, grid, dim3(256), 0, (hipStream_t)stream, descs_dev, (const int*)labels, areas, inf);
+    CRIS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cc_hole_fill_kernel, grid, dim3(256), 0, (hipStream_t)stream, descs_dev, (const int*)labels, (const int*)areas, max_area,
+                       masks, inf);
     CRIS_LAUNCH_CHECK();
     return 0;
 }

@@ -1,5 +1,6 @@
 // Square-structuring-element erosion of the packed masks and the boundary counts built on it: Boundary IoU
-// (Cheng et al., CVPR 2021) for the evaluator, and the first morphology primitive of the mask tool set.
+// (Cheng et al., CVPR 2021) for the evaluator, and the morphology of the mask tool set: cris_morph_masks, further down, chains
+// erosions and dilations over the same planes (opening, closing).
 //
 // The masks are the bytes cris_eval_iou_batch / cris_predict_masks_batch / cris_filter_components leave (descriptor i at d.out_off,
 // d.h_out rows of d.pitch bytes) and, for the ground truth, the staging's packed masks (d.mask_off, the same pitch).  A pixel is
@@ -204,6 +205,104 @@ extern "C" int cris_erode_masks(const unsigned char* masks, size_t mask_bytes, c
     CRIS_LAUNCH_CHECK();
     hipLaunchKernelGGL(morph_unpack_kernel, morph_grid((stride + 1) / 2, 4, n), dim3(256), 0, (hipStream_t)stream, descs_dev, radii_dev, stride,
                        (const morph_word*)raw, (const morph_word*)rowp, boundary, out);
+    CRIS_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- chained operations on the planes: dilation, clipped erosion, and with them opening and closing ----
+// cris_morph_masks packs once (launch 1 above), runs per operation one row pass A -> B and one column pass B -> A over the two planes
+// of `work`, and stores the bytes once.  Every launch reads only what the launch before it wrote, in its own descriptor's slot.
+
+// Row pass of operation `op` (CRIS_MORPH_ERODE / DILATE / ERODE_CLIPPED; uniform over the launch).  Visibility: the kernel boundary.
+// One thread per word: it reads words of its own row of `src` and writes one word of `dst`.
+__global__ __launch_bounds__(256) void morph_row_op_kernel(const cris_eval_desc* __restrict__ descs, const int* __restrict__ radii, int op,
+                                                           size_t stride, const morph_word* __restrict__ src, morph_word* __restrict__ dst) {
+    const cris_eval_desc d = descs[blockIdx.y];
+    const int r = radii[blockIdx.y], wpr = morph_wpr(d);
+    const bool empty = morph_empty(d.h_out, d.w_out, r);
+    const long words = (long)d.h_out * wpr;
+    const size_t slot = (size_t)blockIdx.y * stride;
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < words; t += (long)gridDim.x * blockDim.x) {
+        const long y = t / wpr;
+        const int c = (int)(t % wpr);
+        const uint64_t* row = reinterpret_cast<const uint64_t*>(src + slot + (size_t)y * wpr);
+        dst[slot + t] = op == CRIS_MORPH_ERODE ? (empty ? 0ull : morph_row_word(row, wpr, c, r))
+                                               : morph_row_or_word(row, wpr, d.w_out, c, r, op == CRIS_MORPH_ERODE_CLIPPED);
+    }
+}
+
+// Column pass of operation `op`.  Visibility: the kernel boundary (the row pass wrote every word of `rowp` this launch reads).  One
+// thread per (row pair, word column): it reads words of its column of `rowp` and writes the two words of `dst` - another plane, so no
+// thread reads what a thread of this launch writes.
+__global__ __launch_bounds__(256) void morph_col_op_kernel(const cris_eval_desc* __restrict__ descs, const int* __restrict__ radii, int op,
+                                                           size_t stride, const morph_word* __restrict__ rowp, morph_word* __restrict__ dst) {
+    const cris_eval_desc d = descs[blockIdx.y];
+    const int r = radii[blockIdx.y], wpr = morph_wpr(d), h = d.h_out;
+    const bool empty = morph_empty(h, d.w_out, r);
+    const long items = (long)((h + 1) >> 1) * wpr;
+    const size_t slot = (size_t)blockIdx.y * stride;
+    const uint64_t* __restrict__ rp = reinterpret_cast<const uint64_t*>(rowp + slot);
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < items; t += (long)gridDim.x * blockDim.x) {
+        const int y0 = (int)(t / wpr) * 2, c = (int)(t % wpr);
+        uint64_t e0 = 0, e1 = 0;
+        if (op == CRIS_MORPH_DILATE) morph_col_pair_or(rp, wpr, h, y0, c, r, &e0, &e1);
+        else if (op == CRIS_MORPH_ERODE_CLIPPED) morph_col_pair_and_clipped(rp, wpr, h, y0, c, r, &e0, &e1);
+        else if (!empty) morph_col_pair(rp, wpr, h, y0, c, r, &e0, &e1);
+        const size_t at = slot + (size_t)y0 * wpr + c;
+        dst[at] = e0;
+        if (y0 + 1 < h) dst[at + wpr] = e1;
+    }
+}
+
+// The last launch of cris_morph_masks.  Visibility: the kernel boundary.  One wave per plane word (the walk of launch 1): lane i
+// stores the byte of pixel 64 c + i when that is < w_out - nothing else of `out` is written.
+__global__ __launch_bounds__(256) void morph_store_kernel(const cris_eval_desc* __restrict__ descs, size_t stride, const morph_word* __restrict__ plane,
+                                                          unsigned char* __restrict__ out) {
+    const cris_eval_desc d = descs[blockIdx.y];
+    const int wpr = morph_wpr(d), lane = threadIdx.x & 63;
+    const long words = (long)d.h_out * wpr;
+    const size_t slot = (size_t)blockIdx.y * stride;
+    unsigned char* __restrict__ O = out + d.out_off;
+    for (long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6); t < words; t += (long)gridDim.x * 4) {           // (wave-uniform)
+        const int y = (int)(t / wpr), x = (int)(t % wpr) * 64 + lane;
+        if (x >= d.w_out) continue;
+        O[(size_t)y * d.pitch + x] = (plane[slot + t] >> lane) & 1ull ? 255 : 0;
+    }
+}
+
+extern "C" int cris_morph_masks(const unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev,
+                                int n, const int* ops_host, int n_ops, const int* radii_host, const int* radii_dev, void* work, size_t work_bytes,
+                                unsigned char* out, size_t out_bytes, void* stream) {
+    CRIS_CHECK_ARG(masks && descs_host && descs_dev && ops_host && radii_host && radii_dev && work && out, "null operand");
+    CRIS_CHECK_ARG(n > 0 && n <= 65535, "n must be in 1 .. 65535");
+    CRIS_CHECK_ARG(n_ops >= 1 && n_ops <= CRIS_MORPH_MAX_OPS, "n_ops must be in 1 .. 8");
+    CRIS_CHECK_ARG(((uintptr_t)work & 7) == 0 && ((uintptr_t)radii_dev & 3) == 0, "work must be 8-byte, radii 4-byte aligned");
+    for (int k = 0; k < n_ops; ++k) {
+        CRIS_CHECK_ARG(ops_host[k] == CRIS_MORPH_ERODE || ops_host[k] == CRIS_MORPH_DILATE || ops_host[k] == CRIS_MORPH_ERODE_CLIPPED,
+                       "every operation must be 0 (erode), 1 (dilate) or 2 (clipped erode)");
+        for (int i = 0; i < n; ++i)
+            CRIS_CHECK_ARG(radii_host[(size_t)k * n + i] >= 1 && radii_host[(size_t)k * n + i] <= 65535, "every radius must be in 1 .. 65535");
+    }
+    size_t stride = 0;
+    const char* bad = morph_check(descs_host, radii_host, n, mask_bytes < out_bytes ? mask_bytes : out_bytes, -1, false, 0, &stride);
+    CRIS_CHECK_ARG(!bad, bad);
+    const size_t plane = (size_t)n * stride;                               // words of one plane of the batch
+    CRIS_CHECK_ARG(work_bytes >= 2 * 8 * plane, "the work buffer is too small");
+    morph_word* pa = reinterpret_cast<morph_word*>(work);                   // the masks, and the result of every operation
+    morph_word* pb = pa + plane;                                            // the row pass of the operation under way
+    hipLaunchKernelGGL(morph_pack_kernel, morph_grid(stride, 4, n), dim3(256), 0, (hipStream_t)stream, masks, (const unsigned char*)nullptr,
+                       descs_dev, stride, pa, (morph_word*)nullptr);
+    CRIS_LAUNCH_CHECK();
+    for (int k = 0; k < n_ops; ++k) {
+        hipLaunchKernelGGL(morph_row_op_kernel, morph_grid(stride, 256, n), dim3(256), 0, (hipStream_t)stream, descs_dev,
+                           radii_dev + (size_t)k * n, ops_host[k], stride, (const morph_word*)pa, pb);
+        CRIS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(morph_col_op_kernel, morph_grid((stride + 1) / 2, 256, n), dim3(256), 0, (hipStream_t)stream, descs_dev,
+                           radii_dev + (size_t)k * n, ops_host[k], stride, (const morph_word*)pb, pa);
+        CRIS_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(morph_store_kernel, morph_grid(stride, 4, n), dim3(256), 0, (hipStream_t)stream, descs_dev, stride, (const morph_word*)pa,
+                       out);
     CRIS_LAUNCH_CHECK();
     return 0;
 }

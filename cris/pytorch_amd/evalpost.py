@@ -29,7 +29,13 @@ and the strings of a batch are built there in one vectorised pass.
 `Boundary` is the optional second figure of an evaluation pass, Boundary IoU (Cheng et al., CVPR 2021): IoU restricted to the pixels
 within `radius` of each mask's contour.  `erode_batch` (erosion of the packed masks by a square, or the boundary it leaves) and
 `boundary_iou_batch` (intersection / union counts of the prediction's and the ground truth's boundaries) are three launches each of
-csrc/morph.hip over 64-bit bit planes of the masks - DESIGN.md 9b."""
+csrc/morph.hip over 64-bit bit planes of the masks - DESIGN.md 9b.
+
+`Smooth` is the optional smoothing of a thresholded mask before `Components`: opening (removes specks and thin bridges), closing
+(fills pin-holes and narrow gaps) and hole filling, in that order.  `morph_batch` chains erosions and dilations of the packed masks
+over the same bit planes (`dilate_batch`, `open_batch`, `close_batch`; csrc/morph.hip cris_morph_masks), `fill_holes_batch` labels
+the background with the union-find of `label_components` and fills the components that do not reach the image's frame
+(csrc/evalpost.hip cris_fill_holes), `smooth_batch` applies a spec in place - DESIGN.md 9b."""
 import ctypes as C
 import math
 
@@ -586,3 +592,195 @@ def boundary_iou_batch(pred_masks_u8, descs, gt_masks_u8, radii, counts, row0, w
     hip.call("cris_boundary_iou_batch", ptr(pred_masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n,
              ptr(gt_masks_u8), gt_masks_u8.numel(), host.ctypes.data_as(C.c_void_p), ptr(dev), ptr(work), 8 * work.numel(),
              counts.data_ptr() + 8 * int(row0), counts.shape[0] - int(row0), _stream())
+
+
+MORPH_OPS = {"erode": 0, "dilate": 1, "erode_clipped": 2}     # CRIS_MORPH_* of include/cris_hip.h
+MORPH_MAX_OPS = 8
+MORPH_MAX_RADIUS = 65535
+FILL_FIELDS = ("holes_filled", "pixels_filled", "holes", "error")
+
+
+def _morph_ops(name, ops, n):
+    """the host form of a chain: (int32 [k] operation codes, int32 [k, n] radii) of `ops`, a sequence of (operation, radius or one
+    radius per descriptor).  Host only."""
+    if isinstance(ops, (str, bytes)) or not hasattr(ops, "__len__") or not 1 <= len(ops) <= MORPH_MAX_OPS:
+        raise ValueError("%s: ops must be a sequence of 1 .. %d (operation, radius) pairs, got %r" % (name, MORPH_MAX_OPS, ops))
+    codes = np.zeros(len(ops), np.int32)
+    radii = np.zeros((len(ops), n), np.int32)
+    for k, item in enumerate(ops):
+        if not isinstance(item, (tuple, list)) or len(item) != 2 or item[0] not in MORPH_OPS:
+            raise ValueError("%s: ops[%d] must be (%s, radius), got %r" % (name, k, " | ".join(repr(o) for o in MORPH_OPS), item))
+        given = np.asarray(item[1].cpu().numpy() if torch.is_tensor(item[1]) else item[1])
+        if given.dtype.kind not in "iu" or given.dtype == np.bool_ or given.ndim > 1 or (given.ndim == 1 and given.shape[0] != n):
+            raise ValueError("%s: the radius of ops[%d] must be an integer or one integer per descriptor (%d), got %r" % (name, k, n, item[1]))
+        if (given < 1).any() or (given > MORPH_MAX_RADIUS).any():
+            raise ValueError("%s: every radius must be in 1 .. %d, got %r in ops[%d]" % (name, MORPH_MAX_RADIUS, item[1], k))
+        codes[k] = MORPH_OPS[item[0]]
+        radii[k, :] = given
+    return codes, radii
+
+
+def morph_work(descs, device, out=None):
+    """the scratch of `morph_batch` for this batch (two bit planes, half of `boundary_work`): `out` when it is large enough, a new
+    int64 buffer otherwise.  Nothing has to be zeroed."""
+    words = (hip.load().cris_boundary_work_bytes(C.addressof(descs.descs), descs.n) // 2 + 7) // 8
+    if out is not None and out.numel() >= words:
+        return out
+    return torch.empty(max(words + words // 4, 1), dtype=torch.int64, device=device)
+
+
+def morph_batch(masks_u8, descs, ops, out=None, work=None):
+    """A chain of window operations on every descriptor's mask in the packed buffer `masks_u8` -> a packed uint8 buffer with the same
+    layout, bytes 0 / 255.  ops: a sequence of up to 8 (operation, radius) pairs applied in order, radius an integer >= 1 or one per
+    descriptor (a host sequence), operation one of
+        "erode"          E_r: 1 iff the whole (2 r + 1)-square lies inside the image and is foreground (`erode_batch`'s result)
+        "dilate"         D_r: OR over the square clipped to the image
+        "erode_clipped"  E'_r: AND over the square clipped to the image (= not D_r(not M): nothing outside the image exists)
+    Only the h_out x w_out pixels of every descriptor are written - pitch padding, gaps and tail of `out` keep their bytes (a new
+    buffer is zeroed).  out: a uint8 buffer of at least descs.out_bytes to reuse; `masks_u8` itself works in place.  work: scratch
+    from `morph_work`.  2 + 2 len(ops) launches on the current stream (cris_morph_masks), none depending on the content: the masks
+    become bit planes once, every operation is a row pass and a column pass between two planes, the bytes are written once."""
+    _check_packed("morph_batch", masks_u8, descs)
+    if descs.n < 1:
+        raise ValueError("morph_batch: no descriptors")
+    codes, radii = _morph_ops("morph_batch", ops, descs.n)
+    if out is None:
+        out = torch.zeros(descs.out_bytes, dtype=torch.uint8, device=masks_u8.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < descs.out_bytes or out.device != masks_u8.device:
+        raise ValueError("morph_batch: out must be a contiguous uint8 buffer of at least descs.out_bytes on the masks' device")
+    dev = torch.from_numpy(radii.copy()).pin_memory().to(masks_u8.device, non_blocking=True)
+    work = morph_work(descs, masks_u8.device, work)
+    hip.call("cris_morph_masks", ptr(masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n,
+             codes.ctypes.data_as(C.c_void_p), len(codes), radii.ctypes.data_as(C.c_void_p), ptr(dev), ptr(work), 8 * work.numel(), ptr(out),
+             out.numel(), _stream())
+    return out
+
+
+def dilate_batch(masks_u8, descs, radii, out=None, work=None):
+    """D_r of every mask (`morph_batch` with one "dilate"): four launches"""
+    return morph_batch(masks_u8, descs, [("dilate", radii)], out=out, work=work)
+
+
+def open_batch(masks_u8, descs, radii, out=None, work=None):
+    """open_r = D_r(E_r(M)) - scipy.ndimage.binary_opening with a full (2 r + 1)-square: removes what the square does not fit into
+    (specks, thin bridges); anti-extensive and idempotent.  Six launches."""
+    return morph_batch(masks_u8, descs, [("erode", radii), ("dilate", radii)], out=out, work=work)
+
+
+def close_batch(masks_u8, descs, radii, out=None, work=None):
+    """close_r = E'_r(D_r(M)) - binary_erosion(binary_dilation(M, S), S, border_value=1): fills what the square does not fit into
+    (pin-holes, narrow gaps); extensive also for objects that touch the image border, and idempotent.  NOT scipy's binary_closing
+    default, whose erosion takes the outside for background and eats objects at the border.  Six launches."""
+    return morph_batch(masks_u8, descs, [("dilate", radii), ("erode_clipped", radii)], out=out, work=work)
+
+
+def fill_work(descs, device, out=None):
+    """the scratch of `fill_holes_batch` for this batch (one word per mask byte): `out` when it is large enough, a new int64 buffer
+    otherwise.  The launcher zeroes it itself."""
+    words = (hip.load().cris_fill_holes_work_bytes(descs.out_bytes) + 7) // 8
+    if out is not None and out.numel() >= words:
+        return out
+    return torch.empty(max(words + words // 4, 2), dtype=torch.int64, device=device)
+
+
+def fill_holes_batch(masks_u8, descs, info, row0, connectivity=4, max_area=None, labels=None, work=None):
+    """Fill the holes of every descriptor's mask in the packed buffer IN PLACE: a hole is a connected component of the background
+    (connectivity 4, or 8) that holds no pixel of the image's outer frame; every pixel of a hole of at most `max_area` pixels (None:
+    of every hole) becomes 255, no other byte changes.  connectivity=4, max_area=None is scipy.ndimage.binary_fill_holes.  info:
+    [R, 4] cuda int64 zeroed by the caller once per pass; info[row0 + row] += (holes_filled, pixels_filled, holes, error)
+    (FILL_FIELDS; `check_component_info` reads the error column).  labels: an int32 buffer of at least descs.out_bytes words to reuse
+    (it receives the labels of the BACKGROUND); work: scratch from `fill_work`.  Five launches and one memset on the current stream
+    (cris_fill_holes), none depending on the content.  Descriptors must not alias one rectangle."""
+    _check_packed("fill_holes_batch", masks_u8, descs)
+    if descs.n < 1:
+        raise ValueError("fill_holes_batch: no descriptors")
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError("fill_holes_batch: connectivity must be 4 or 8, got %r" % (connectivity,))
+    if max_area is not None and (isinstance(max_area, bool) or not isinstance(max_area, (int, np.integer)) or max_area < 0):
+        raise ValueError("fill_holes_batch: max_area must be None or an integer >= 0, got %r" % (max_area,))
+    if info.dtype != torch.int64 or info.dim() != 2 or info.shape[1] != 4 or not info.is_contiguous() or not 0 <= row0 < info.shape[0]:
+        raise ValueError("fill_holes_batch: info must be contiguous int64 [R, 4] and row0 inside it")
+    if labels is None:
+        labels = torch.empty(descs.out_bytes, dtype=torch.int32, device=masks_u8.device)
+    elif labels.dtype != torch.int32 or labels.dim() != 1 or not labels.is_contiguous() or labels.numel() < descs.out_bytes or labels.device != masks_u8.device:
+        raise ValueError("fill_holes_batch: labels must be a contiguous int32 buffer of at least descs.out_bytes words on the masks' device")
+    work = fill_work(descs, masks_u8.device, work)
+    hip.call("cris_fill_holes", ptr(masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n, int(connectivity),
+             -1 if max_area is None else min(int(max_area), 2 ** 31 - 1), ptr(labels), labels.numel(), ptr(work), 8 * work.numel(),
+             info.data_ptr() + 32 * int(row0), info.shape[0] - int(row0), _stream())
+
+
+class Smooth:
+    """Mask smoothing after the threshold, as a validated value (the style of `Components`).  The order is fixed: opening by the
+    (2 open + 1)-square (removes specks and thin bridges), then closing by the (2 close + 1)-square (fills pin-holes and narrow gaps;
+    `close_batch`: objects at the image border are kept), then hole filling (holes of at most `max_hole_area` pixels, None = all;
+    background connectivity `hole_connectivity`), then - where the entry point takes one - the `Components` filter.  Radii are
+    integers in pixels at the image's own size; 0 means off.  Host only."""
+
+    __slots__ = ("open", "close", "fill_holes", "max_hole_area", "hole_connectivity")
+
+    def __init__(self, open=0, close=0, fill_holes=False, max_hole_area=None, hole_connectivity=4):
+        for name, r in (("open", open), ("close", close)):
+            if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= r <= MORPH_MAX_RADIUS:
+                raise ValueError("Smooth: %s must be an integer radius in 0 .. %d, got %r" % (name, MORPH_MAX_RADIUS, r))
+        if not isinstance(fill_holes, (bool, np.bool_)):
+            raise ValueError("Smooth: fill_holes must be True or False, got %r" % (fill_holes,))
+        if max_hole_area is not None and (isinstance(max_hole_area, bool) or not isinstance(max_hole_area, (int, np.integer)) or max_hole_area < 1):
+            raise ValueError("Smooth: max_hole_area must be None or an integer >= 1, got %r" % (max_hole_area,))
+        if max_hole_area is not None and not fill_holes:
+            raise ValueError("Smooth: max_hole_area needs fill_holes=True")
+        if isinstance(hole_connectivity, bool) or hole_connectivity not in (4, 8):
+            raise ValueError("Smooth: hole_connectivity must be 4 or 8, got %r" % (hole_connectivity,))
+        object.__setattr__(self, "open", int(open))
+        object.__setattr__(self, "close", int(close))
+        object.__setattr__(self, "fill_holes", bool(fill_holes))
+        object.__setattr__(self, "max_hole_area", None if max_hole_area is None else int(max_hole_area))
+        object.__setattr__(self, "hole_connectivity", int(hole_connectivity))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Smooth is immutable")
+
+    def _key(self):
+        return (self.open, self.close, self.fill_holes, self.max_hole_area, self.hole_connectivity)
+
+    @property
+    def is_noop(self):
+        """both radii 0 and no hole filling: nothing changes"""
+        return self.open == 0 and self.close == 0 and not self.fill_holes
+
+    @property
+    def ops(self):
+        """the window operations of the spec as `morph_batch` takes them: () when both radii are 0"""
+        return (((("erode", self.open), ("dilate", self.open)) if self.open else ())
+                + ((("dilate", self.close), ("erode_clipped", self.close)) if self.close else ()))
+
+    def __eq__(self, other):
+        return isinstance(other, Smooth) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "Smooth(open=%d, close=%d, fill_holes=%r, max_hole_area=%r, hole_connectivity=%d)" % self._key()
+
+
+def smooth_spec(value, what="smooth"):
+    """None or a Smooth -> the spec to apply, or None when there is nothing to do (a spec that changes nothing is no spec); anything
+    else is a ValueError.  Host only: callers run this before they touch a device."""
+    if value is None:
+        return None
+    if not isinstance(value, Smooth):
+        raise ValueError("%s must be None or an evalpost.Smooth, got %r" % (what, value))
+    return None if value.is_noop else value
+
+
+def smooth_batch(masks_u8, descs, spec, info, row0, labels=None, work=None, fwork=None):
+    """Apply `spec` (a Smooth) to the packed masks IN PLACE on the current stream: `morph_batch` with the spec's operations (open,
+    then close - one chain, the masks are packed to bit planes and written back once), then `fill_holes_batch`.  info / row0 /
+    labels / fwork: as for `fill_holes_batch` (the table is touched only with fill_holes); work: scratch from `morph_work`."""
+    if not isinstance(spec, Smooth):
+        raise ValueError("smooth_batch: spec must be an evalpost.Smooth, got %r" % (spec,))
+    if spec.ops:
+        morph_batch(masks_u8, descs, spec.ops, out=masks_u8, work=work)
+    if spec.fill_holes:
+        fill_holes_batch(masks_u8, descs, info, row0, spec.hole_connectivity, spec.max_hole_area, labels=labels, work=fwork)

@@ -22,6 +22,10 @@ in place and `evalpost.mask_iou_batch` adds the counts of the filtered masks to 
 (Cheng et al., CVPR 2021) - the masks the batch wrote (filtered when `components` is given) and the ground truth are eroded on the
 device and `evalpost.boundary_iou_batch` adds (intersection, union) of the two boundaries to a second table, read with the first;
 `boundary_counts`, `boundary_per_sample`, `boundary_iou` and `boundary_prec` hold the result (`metrics` of that table).
+
+`validate` / `inference` take `smooth=evalpost.Smooth(...)`: every predicted mask is opened, closed and has its holes filled on the
+device (in that order, before `components`) and the final masks are counted; the ground truth is never smoothed; `smooth_info`
+holds the holes and pixels filled per sample.
 """
 import math
 
@@ -181,6 +185,8 @@ class Evaluator:
         self._cc_masks = self._cc_labels = self._cc_work = self._cc_counts = None      # component clean-up scratch, reused across batches
         self.boundary_counts = self.boundary_per_sample = self.boundary_iou = self.boundary_prec = None
         self._bd_masks = self._bd_work = None                      # boundary scratch (the batch's masks, the bit planes), likewise
+        self.smooth_info = None
+        self._sm_work = None                                       # smoothing scratch (two bit planes), likewise
 
     def _staging(self):
         self._turn = (self._turn + 1) % self.RING
@@ -194,9 +200,10 @@ class Evaluator:
                 raise ValueError("record %s: mask is %s, image %s" % (p["mask_dir"], tuple(m.shape), tuple(p["ori_size"])))
         return masks
 
-    def _clean_counts(self, spec, probs, st, table, row0, info, out=None):
-        """one batch with a Components spec: iou_batch writes the masks (its own counts go to a scratch table), the filter rewrites
-        them in place, mask_iou_batch adds the filtered masks' counts to `table`.  out=None: an internal, reused mask buffer."""
+    def _clean_counts(self, spec, probs, st, table, row0, info, out=None, sspec=None, sinfo=None):
+        """one batch with a Components and / or a Smooth spec: iou_batch writes the masks (its own counts go to a scratch table), the
+        smoothing (open, close, fill holes) and then the filter rewrite them in place, mask_iou_batch adds the final masks' counts to
+        `table`.  The ground truth is never touched.  out=None: an internal, reused mask buffer."""
         if out is None:
             if self._cc_masks is None or self._cc_masks.numel() < st.out_bytes:
                 self._cc_masks = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.uint8, device=self.device)
@@ -207,8 +214,13 @@ class Evaluator:
             self._cc_counts = torch.zeros(table.shape[0] - row0, 2, dtype=torch.int32, device=self.device)
         self._cc_work = evalpost.filter_work(st, self.device, self._cc_work)
         evalpost.iou_batch(probs, st, st.masks, self._cc_counts, 0, self.thr, out_masks=out)
-        labels = evalpost.label_components(out, st, spec.connectivity, out=self._cc_labels)
-        evalpost.filter_components(out, labels, st, spec, info, row0, work=self._cc_work)
+        if sspec is not None:
+            if sspec.ops:
+                self._sm_work = evalpost.morph_work(st, self.device, self._sm_work)
+            evalpost.smooth_batch(out, st, sspec, sinfo, row0, labels=self._cc_labels, work=self._sm_work, fwork=self._cc_work)
+        if spec is not None:
+            labels = evalpost.label_components(out, st, spec.connectivity, out=self._cc_labels)
+            evalpost.filter_components(out, labels, st, spec, info, row0, work=self._cc_work)
         evalpost.mask_iou_batch(out, st, st.masks, table, row0)
         return out
 
@@ -238,6 +250,12 @@ class Evaluator:
         """the pass's read of the component table (after the counts'): raises when an error column is set"""
         self.component_info = evalpost.check_component_info(info[:n].cpu().numpy())
 
+    def _finish_smooth(self, sinfo, n):
+        """the pass's read of the hole table (None: a pass without the spec): [n, 2] holes and pixels filled per sample"""
+        self.smooth_info = None
+        if sinfo is not None:
+            self.smooth_info = evalpost.check_component_info(sinfo[:n].cpu().numpy())[:, :2].copy()
+
     def _finish(self, table, n, group):
         counts = gather_counts(table[:n].cpu(), group)             # the pass's one host read
         iou, prec, per = metrics(counts.numpy())
@@ -246,13 +264,16 @@ class Evaluator:
         return iou, prec
 
     @torch.no_grad()
-    def validate(self, records, indices=None, batch_size=32, group=None, components=None, boundary=None):
+    def validate(self, records, indices=None, batch_size=32, group=None, components=None, boundary=None, smooth=None):
         """components: None or an evalpost.Components - clean every predicted mask up before it is counted (`component_info`
         then holds the [n, 4] table of evalpost.INFO_FIELDS per sample).  boundary: None, True or an evalpost.Boundary - also
         count Boundary IoU of the (cleaned) masks: `boundary_iou`, `boundary_prec`, `boundary_per_sample`, `boundary_counts`;
-        the return value stays (iou, prec) of the masks."""
+        the return value stays (iou, prec) of the masks.  smooth: None or an evalpost.Smooth - open, close and fill the holes of
+        every predicted mask on the device before `components` and before anything is counted (`smooth_info` then holds the
+        [n, 2] holes and pixels filled per sample); the ground truth is never smoothed."""
         spec = evalpost.components_spec(components, "validate: components")
         bspec = evalpost.boundary_spec(boundary, "validate: boundary")
+        sspec = evalpost.smooth_spec(smooth, "validate: smooth")
         if self.pipe.mode != "val":
             raise ValueError("validate needs a RecordPipeline in mode 'val'")
         indices = list(range(len(records))) if indices is None else [int(i) for i in indices]
@@ -261,6 +282,7 @@ class Evaluator:
         table = torch.zeros(len(indices), 2, dtype=torch.int32, device=self.device)
         info = None if spec is None else torch.zeros(len(indices), 4, dtype=torch.int64, device=self.device)
         btable = None if bspec is None else torch.zeros(len(indices), 2, dtype=torch.int32, device=self.device)
+        sinfo = None if sspec is None else torch.zeros(len(indices), 4, dtype=torch.int64, device=self.device)
         for lo in range(0, len(indices), batch_size):
             recs = [records[i] for i in indices[lo:lo + batch_size]]
             img, word, params = self.pipe(recs)
@@ -270,25 +292,28 @@ class Evaluator:
                 img, word = img[rep], word[rep]
             st = self._staging().pack(*plan_validate(self._masks(recs, params), [p["inverse"] for p in params])).upload()
             probs = evalpost.sigmoid_upsample(self.model(img, word), img.shape[-2], img.shape[-1])
-            if spec is None:
+            if spec is None and sspec is None:
                 out = None if bspec is None else self._boundary_masks(st)
                 evalpost.iou_batch(probs, st, st.masks, table, lo, self.thr, out_masks=out)
             else:
-                out = self._clean_counts(spec, probs, st, table, lo, info)
+                out = self._clean_counts(spec, probs, st, table, lo, info, sspec=sspec, sinfo=sinfo)
             if bspec is not None:
                 self._boundary_counts(bspec, out, st, btable, lo)
         result = self._finish(table, len(indices), group)
         self._finish_boundary(btable, len(indices), group, True)
+        self._finish_smooth(sinfo, len(indices))
         if spec is not None:
             self._finish_components(info, len(indices))
         return result
 
     @torch.no_grad()
-    def inference(self, records, indices=None, images_per_batch=8, visualize=None, components=None, boundary=None):
+    def inference(self, records, indices=None, images_per_batch=8, visualize=None, components=None, boundary=None, smooth=None):
         """components: as for `validate`; a `visualize` callback then receives the FILTERED masks and their IoUs.  boundary: as for
-        `validate` (the expressions of one image share its ground truth)"""
+        `validate` (the expressions of one image share its ground truth).  smooth: as for `validate`; the callback receives the
+        smoothed masks."""
         spec = evalpost.components_spec(components, "inference: components")
         bspec = evalpost.boundary_spec(boundary, "inference: boundary")
+        sspec = evalpost.smooth_spec(smooth, "inference: smooth")
         if self.pipe.mode != "test":
             raise ValueError("inference needs a RecordPipeline in mode 'test'")
         indices = list(range(len(records))) if indices is None else [int(i) for i in indices]
@@ -299,6 +324,7 @@ class Evaluator:
         table = torch.zeros(total, 2, dtype=torch.int32, device=self.device)
         info = None if spec is None else torch.zeros(total, 4, dtype=torch.int64, device=self.device)
         btable = None if bspec is None else torch.zeros(total, 2, dtype=torch.int32, device=self.device)
+        sinfo = None if sspec is None else torch.zeros(total, 4, dtype=torch.int64, device=self.device)
         row0 = 0
         for recs in batches:
             img, params = self.pipe(recs)
@@ -319,12 +345,12 @@ class Evaluator:
                 logits = self.model(img[torch.tensor(index, device=self.device)], word)
             probs = evalpost.sigmoid_upsample(logits, img.shape[-2], img.shape[-1])
             out = None if visualize is None else torch.empty(st.out_bytes, dtype=torch.uint8, device=self.device)
-            if spec is None:
+            if spec is None and sspec is None:
                 if out is None and bspec is not None:
                     out = self._boundary_masks(st)
                 evalpost.iou_batch(probs, st, st.masks, table, row0, self.thr, out_masks=out)
             else:
-                out = self._clean_counts(spec, probs, st, table, row0, info, out)
+                out = self._clean_counts(spec, probs, st, table, row0, info, out, sspec=sspec, sinfo=sinfo)
             if bspec is not None:
                 self._boundary_counts(bspec, out, st, btable, row0)
             if visualize is not None:
@@ -332,6 +358,7 @@ class Evaluator:
             row0 += K
         result = self._finish(table, total, None)
         self._finish_boundary(btable, total, None, False)
+        self._finish_smooth(sinfo, total)
         if spec is not None:
             self._finish_components(info, total)
         return result

@@ -367,6 +367,9 @@ _SIGS = {
     "cris_boundary_work_bytes": (C.c_size_t, [P, I]),
     "cris_erode_masks": (I, [P, C.c_size_t, P, P, I, P, P, P, C.c_size_t, P, C.c_size_t, I, P]),
     "cris_boundary_iou_batch": (I, [P, C.c_size_t, P, P, I, P, C.c_size_t, P, P, P, C.c_size_t, P, I, P]),
+    "cris_morph_masks": (I, [P, C.c_size_t, P, P, I, P, I, P, P, P, C.c_size_t, P, C.c_size_t, P]),
+    "cris_fill_holes_work_bytes": (C.c_size_t, [C.c_size_t]),
+    "cris_fill_holes": (I, [P, C.c_size_t, P, P, I, I, I, P, C.c_size_t, P, C.c_size_t, P, I, P]),
     "cris_preprocess_batch": (I, [P, I, I, I, P, P, P, P, P, P, P, P]),
     "cris_gray_sum_batch": (I, [P, P, I, P, P]),
     "cris_preprocess_batch_aug": (I, [P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),

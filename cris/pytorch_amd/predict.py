@@ -17,12 +17,15 @@ up; the table of the whole call comes back once at the end, the masks once per b
 (connected components: DESIGN.md 9b): the masks of a batch stay in a device buffer, `evalpost.label_components` and
 `evalpost.filter_components` run on the stream, and the call returns ComponentPrediction - area, box and score of the KEPT pixels.
 
+`smooth=evalpost.Smooth(open=R, close=R, fill_holes=True)` smooths every mask on the device right after the threshold (opening, closing,
+hole filling: DESIGN.md 9b), before the clean-up; area, box and score are then those of the pixels finally set (ComponentPrediction).
+
 `masks="rle"` ends that chain on the device too: the masks of a batch stay in an internal device buffer, `evalpost.rle_encode_batch`
 finds their run-length transitions (csrc/rle.hip) and `Prediction.mask` is the COCO RLE dict of rle.py - a few hundred bytes per
 mask cross to the host instead of the image-sized mask.  `coco_results` turns such a result into the list a results file holds.
 
     python -m cris.pytorch_amd.predict --weights CKPT --config YAML --image F --expr "the left one" --out-prefix P [--keep largest]
-                                       [--rle-json RESULTS.json]
+                                       [--rle-json RESULTS.json] [--open R] [--close R] [--fill-holes] [--max-hole-area N]
 """
 from collections import namedtuple
 
@@ -86,6 +89,13 @@ def _check_components(value, default):
     return evalpost.components_spec(value, "predict: components")
 
 
+def _check_smooth(value, default):
+    """the smoothing of one call: "default" -> the constructor's; None / a no-op spec -> None (host only)"""
+    if isinstance(value, str) and value == "default":
+        return default
+    return evalpost.smooth_spec(value, "predict: smooth")
+
+
 def _check_inputs(images, expressions, images_per_batch, masks):
     """-> (kind 'bytes' / 'array', expressions as lists); everything here is host-only"""
     if masks not in MASK_MODES:
@@ -116,15 +126,16 @@ def _check_inputs(images, expressions, images_per_batch, masks):
 
 
 class Predictor:
-    """`Predictor(model, pipeline, thr=0.35, components=None)`: model - an InferenceRunner, the drop-in CRIS module in eval mode, or any callable
+    """`Predictor(model, pipeline, thr=0.35, components=None, smooth=None)`: model - an InferenceRunner, the drop-in CRIS module in eval mode, or any callable
     `(img, word) -> logits [B, 1, h, w]`; when it offers `segment(img, word, image_index)` or `segment_expressions`, the visual
     encoder runs once per image, otherwise `model(img[index], word)` is called.  pipeline - a RecordPipeline in mode "test" (its
     preprocessor, tokenizer, word length and decode threads are used; no record is needed).  components - None or an
-    evalpost.Components: the mask clean-up `predict` applies unless the call names another."""
+    evalpost.Components: the mask clean-up `predict` applies unless the call names another.  smooth - None or an evalpost.Smooth:
+    the smoothing (open, close, fill holes) `predict` applies before that clean-up unless the call names another."""
 
     RING = 3            # descriptor staging buffers in flight (evaluate.Evaluator.RING)
 
-    def __init__(self, model, pipeline, thr=0.35, components=None):
+    def __init__(self, model, pipeline, thr=0.35, components=None, smooth=None):
         if getattr(pipeline, "mode", None) != "test":
             raise ValueError("Predictor needs a RecordPipeline in mode 'test', got %r" % (getattr(pipeline, "mode", None),))
         thr = float(thr)
@@ -132,11 +143,14 @@ class Predictor:
             raise ValueError("Predictor: thr must be finite and >= 0, got %r" % (thr,))
         self.model, self.pipe, self.thr = model, pipeline, thr
         self.components = evalpost.components_spec(components, "Predictor: components")
+        self.smooth = evalpost.smooth_spec(smooth, "Predictor: smooth")
+        self.smooth_info = None                                       # after a call with a Smooth spec: [total, 2] holes, pixels filled
         self.device = pipeline.device
         self._segment = getattr(model, "segment", None) or getattr(model, "segment_expressions", None)
         self._ring, self._turn = None, 0
         self._cc_masks = self._cc_labels = self._cc_work = None       # component clean-up scratch, reused across batches
         self._rle_runs = self._rle_work = None                        # run-length encoder buffers, reused across batches
+        self._sm_work = None                                          # smoothing scratch (two bit planes), reused across batches
 
     def _staging(self):
         if self._ring is None:          # (the first device allocation: after every argument check)
@@ -170,7 +184,7 @@ class Predictor:
         return out
 
     @torch.no_grad()
-    def predict(self, images, expressions, images_per_batch=8, masks="host", components="default"):
+    def predict(self, images, expressions, images_per_batch=8, masks="host", components="default", smooth="default"):
         """images: JPEG bytes per image, or uint8 RGB [h, w, 3] arrays / tensors per image (one kind per call; JPEG files come
         back turned by their EXIF orientation, as cv2.imdecode returns them).  expressions: per image a str or a non-empty list
         of str.  masks: "host" (numpy arrays, one device-to-host copy per batch), "device" (views of one CUDA buffer per batch),
@@ -179,9 +193,18 @@ class Predictor:
         of Prediction per expression.
         components: an evalpost.Components, None (no clean-up) or "default" (the constructor's).  With a spec every mask is
         labelled and filtered on the device before anything is read, the statistics are those of the kept pixels and the entries
-        are ComponentPrediction; with masks=None the masks live in an internal device buffer and never reach the host."""
+        are ComponentPrediction; with masks=None the masks live in an internal device buffer and never reach the host.
+        smooth: an evalpost.Smooth, None (no smoothing) or "default" (the constructor's).  With a spec every mask is opened, closed
+        and has its holes filled in place on the device (in that order) right after the threshold, then labelled and filtered
+        (`components`, or a filter that keeps everything): the entries are ComponentPrediction whose area, box and score are those
+        of the pixels finally set - filled pixels count with their own probability, whatever the threshold - n_components counts the
+        components of the smoothed mask and raw_area is the thresholded area before any of it; masks="rle" encodes the final mask;
+        `smooth_info` holds the [total, 2] holes and pixels filled per expression."""
         from . import jpegdec
         spec = _check_components(components, self.components)
+        sspec = _check_smooth(smooth, self.smooth)
+        if sspec is not None and spec is None:
+            spec = evalpost.Components()                               # keeps everything: labels, statistics of the final pixels
         kind, images, exprs = _check_inputs(images, expressions, images_per_batch, masks)
         images_per_batch = int(images_per_batch)
         plans = plan_predict([len(e) for e in exprs], images_per_batch)
@@ -190,6 +213,7 @@ class Predictor:
         if spec is not None:
             ktable = evalpost.new_predict_stats(total, self.device)    # statistics of the kept pixels
             info = torch.zeros(total, 4, dtype=torch.int64, device=self.device)
+        sinfo = None if sspec is None else torch.zeros(total, 4, dtype=torch.int64, device=self.device)
         kept = []                                                      # per expression: its mask (or None)
         for b in plans:
             part = images[b.lo:b.lo + b.n]
@@ -216,6 +240,10 @@ class Predictor:
             if spec is not None:
                 out = self._component_buffers(st, out)
             evalpost.predict_batch(probs, st, table, 0, self.thr, out_masks=out)
+            if sspec is not None:
+                if sspec.ops:
+                    self._sm_work = evalpost.morph_work(st, self.device, self._sm_work)
+                evalpost.smooth_batch(out, st, sspec, sinfo, 0, labels=self._cc_labels, work=self._sm_work, fwork=self._cc_work)
             if spec is not None:
                 labels = evalpost.label_components(out, st, spec.connectivity, out=self._cc_labels)
                 evalpost.filter_components(out, labels, st, spec, info, 0, probs=probs, stats=ktable, work=self._cc_work)
@@ -230,6 +258,11 @@ class Predictor:
                 d = st.descs[k]
                 m = buf[d.out_off:d.out_off + d.pitch * d.h_out].reshape(d.h_out, d.pitch)[:, :d.w_out]
                 kept.append(np.ascontiguousarray(m) if masks == "host" else m)
+        self.smooth_info = None
+        if sspec is not None:
+            rows = torch.cat([ktable, info, table[:, :1], sinfo], 1).cpu().numpy()     # the call's one read
+            self.smooth_info = evalpost.check_component_info(rows[:, 11:15])[:, :2].copy()
+            return self._component_result(exprs, kept, rows[:, :11], smoothed=True)
         if spec is not None:
             return self._component_result(exprs, kept, torch.cat([ktable, info, table[:, :1]], 1).cpu().numpy())
         stats = table.cpu().numpy()                                    # the call's one read of the statistics
@@ -245,15 +278,19 @@ class Predictor:
 
 
     @staticmethod
-    def _component_result(exprs, kept, rows):
-        """rows: [total, 11] = kept statistics (6), info (4), raw area - the call's one read, the error column checked here"""
+    def _component_result(exprs, kept, rows, smoothed=False):
+        """rows: [total, 11] = kept statistics (6), info (4), raw area - the call's one read, the error column checked here.
+        smoothed: the labelled mask is the smoothed one, so raw_area is the thresholded area of the plain table and is not compared
+        with the labelled foreground"""
         evalpost.check_component_info(rows[:, 6:10])
         result, k = [], 0
         for e in exprs:
             row = []
             for s in e:
                 area, q16, x0, y0, x1, y1, n_comp, _, raw, _, raw_stats = (int(v) for v in rows[k])
-                if raw != raw_stats:
+                if smoothed:
+                    raw = raw_stats
+                elif raw != raw_stats:
                     raise RuntimeError("predict: the labelled foreground (%d pixels) is not the thresholded mask (%d)" % (raw, raw_stats))
                 row.append(ComponentPrediction(s, kept[k], area, (x0, y0, x1, y1) if area else None,
                                                q16 / (65536.0 * area) if area else 0.0, n_comp, raw))
@@ -337,9 +374,14 @@ def main(argv=None):
                     help="connected-component clean-up of every mask: 'largest' keeps the largest component only")
     ap.add_argument("--min-area", type=int, default=0, metavar="N", help="drop components of fewer than N pixels")
     ap.add_argument("--connectivity", type=int, choices=(4, 8), default=8, help="pixels connect through edges (4) or edges and corners (8)")
+    ap.add_argument("--open", type=int, default=0, metavar="R", help="open every mask by the (2 R + 1)-square first: removes specks and thin bridges")
+    ap.add_argument("--close", type=int, default=0, metavar="R", help="then close it by the (2 R + 1)-square: fills pin-holes and narrow gaps")
+    ap.add_argument("--fill-holes", action="store_true", help="then fill the holes: background that does not reach the image's frame")
+    ap.add_argument("--max-hole-area", type=int, default=None, metavar="N", help="fill only holes of at most N pixels (with --fill-holes)")
     a = ap.parse_args(argv)
     try:
         spec = evalpost.Components(a.keep, a.min_area, a.connectivity)
+        smooth = evalpost.Smooth(a.open, a.close, a.fill_holes, a.max_hole_area)
     except ValueError as e:
         ap.error(str(e))
     if not a.out_prefix and not a.rle_json:
@@ -369,7 +411,7 @@ def main(argv=None):
     with open(a.image, "rb") as f:
         data = f.read()
     image = data if data[:2] == b"\xff\xd8" else np.array(Image.open(a.image).convert("RGB"))
-    predictor = Predictor(runner, pipe, thr=a.thr, components=spec)
+    predictor = Predictor(runner, pipe, thr=a.thr, components=spec, smooth=smooth)
     if a.rle_json:
         import json
         encoded = predictor.predict([image], [a.expr], images_per_batch=1, masks="rle")

@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_rle_encode / cris_rle_work_bytes (COCO run-length encoding of the packed masks on the device) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/rle.hip), every other launcher keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_erode_masks / cris_boundary_iou_batch / cris_boundary_work_bytes (square-structuring-element erosion of the packed masks and the Boundary IoU counts built on it) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/morph.hip), the radii travel as a separate int32 array, every other launcher keeps its signature, its kernel and its results, and a binding that knows the three binds them at load, so a library without them is refused there */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_rle_encode / cris_rle_work_bytes (COCO run-length encoding of the packed masks on the device) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/rle.hip), every other launcher keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_erode_masks / cris_boundary_iou_batch / cris_boundary_work_bytes (square-structuring-element erosion of the packed masks and the Boundary IoU counts built on it) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/morph.hip), the radii travel as a separate int32 array, every other launcher keeps its signature, its kernel and its results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_morph_masks / cris_fill_holes / cris_fill_holes_work_bytes (mask smoothing: chained dilation / erosion of the packed masks, hence opening and closing, and hole filling) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc, the operation codes and radii travel as separate int32 arrays, cris_erode_masks / cris_boundary_iou_batch / cris_label_components / cris_filter_components keep their signatures, their launches and their results, and a binding that knows the three binds them at load, so a library without them is refused there */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -630,6 +630,43 @@ int cris_erode_masks(const unsigned char* masks, size_t mask_bytes, const cris_e
 int cris_boundary_iou_batch(const unsigned char* pred, size_t pred_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev,
                             int n, const unsigned char* gt, size_t gt_bytes, const int* radii_host, const int* radii_dev, void* work,
                             size_t work_bytes, int* counts, int count_rows, void* stream);
+/* Mask smoothing on the same packed masks (csrc/morph.hip, csrc/evalpost.hip; DESIGN.md 9b): a chain of window operations, and hole
+ * filling.  With W_r(p) the (2 r + 1)-square around p CLIPPED to the image (nothing outside the image exists),
+ *     CRIS_MORPH_ERODE          E_r   as above: background outside the image (cris_erode_masks' result, bit for bit)
+ *     CRIS_MORPH_DILATE         D_r(M)[p]  = OR  of M over W_r(p)
+ *     CRIS_MORPH_ERODE_CLIPPED  E'_r(M)[p] = AND of M over W_r(p) = ~D_r(~M) on the image (binary_erosion with border_value = 1)
+ * so open_r = D_r E_r (scipy's binary_opening with a full square; anti-extensive, idempotent) and close_r = E'_r D_r (extensive also
+ * for objects at the image border, idempotent; NOT scipy's binary_closing default, whose second step erodes from the border).
+ * cris_morph_masks applies ops_host[0], then ops_host[1], ... (1 <= n_ops <= CRIS_MORPH_MAX_OPS) with the radius
+ * radii[k * n + i] of operation k on descriptor i (radii_host is checked here, radii_dev - the same n_ops * n values in device memory -
+ * is read by the kernels; every value in 1 .. 65535) and writes bytes 0 / 255 at out_off / pitch of `out`; no byte outside a
+ * descriptor's h_out x w_out pixels is written, out == masks is allowed, descriptors may alias one rectangle.  work: two bit planes,
+ * cris_boundary_work_bytes(descs_host, n) / 2 bytes, nothing has to be zeroed.  2 + 2 n_ops launches on the stream (pack; per
+ * operation a row pass plane A -> B and a column pass B -> A; store), none depending on the content, integers only.  Checked on the
+ * host before the first launch: operands non-NULL, n, n_ops, every operation code, every radius, alignment (work 8-byte, radii_dev
+ * 4-byte), work_bytes, and per descriptor what cris_erode_masks checks. */
+#define CRIS_MORPH_ERODE 0
+#define CRIS_MORPH_DILATE 1
+#define CRIS_MORPH_ERODE_CLIPPED 2
+#define CRIS_MORPH_MAX_OPS 8
+int cris_morph_masks(const unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev, int n,
+                     const int* ops_host, int n_ops, const int* radii_host, const int* radii_dev, void* work, size_t work_bytes,
+                     unsigned char* out, size_t out_bytes, void* stream);
+/* cris_fill_holes, in place: a hole is a connected component of the BACKGROUND (byte == 0, x < w_out; connectivity 4 or 8) that holds no
+ * pixel of the image's outer frame (row 0, row h_out - 1, column 0, column w_out - 1); every pixel of a hole of at most max_area pixels
+ * (max_area = -1: of any hole) becomes 255, no other byte is written.  connectivity 4, max_area -1 is scipy's binary_fill_holes.
+ * The background is labelled by cris_label_components' three launches into `labels` (one int32 word per mask byte; the words of
+ * foreground pixels and padding become -1); then `work` (cris_fill_holes_work_bytes(mask_bytes) bytes: one word per mask byte) is zeroed
+ * by a memset on the stream, one launch adds every background pixel to its root's area and marks the roots that own a frame pixel,
+ * and one launch writes the holes.  info: int64 table [info_rows][4], descriptor d adds to row d.row (holes_filled, pixels_filled,
+ * holes = all holes whatever their area, error = 1 when a label carries the union-find's cap mark); the caller zeroes it.  Integer
+ * atomics only: the same masks and tables on every run.  Checked on the host first: operands non-NULL, n in 1 .. 65535, connectivity,
+ * max_area >= -1, alignment (masks 4-byte; labels, work 16-byte; info 8-byte), label_words >= mask_bytes, work_bytes, row < info_rows,
+ * and per descriptor what cris_label_components checks.  Descriptors must not alias. */
+size_t cris_fill_holes_work_bytes(size_t mask_bytes);
+int cris_fill_holes(unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev, int n,
+                    int connectivity, int max_area, int* labels, size_t label_words, void* work, size_t work_bytes, long long* info,
+                    int info_rows, void* stream);
 /* ---- input preprocessing (reference utils/dataset.py:146-168 RefDataset.__getitem__, :207-221 convert; csrc/inputpipe.hip) ----
  * One launch per batch: img_out[b] = ((cv2.warpAffine(rgb_u8, mat, (S_w, S_h), INTER_CUBIC, borderValue=border_rgb).float()
  * / 255 - mean) / std) as [3][S_h][S_w] (through lut_img [3][256]), mask_out[b] = cv2.warpAffine(mask_u8, mat, ...,

@@ -24,7 +24,13 @@ masks have structure (synthetic weights put every pixel above 0.35).
 replaces) and masks="rle"; the encoder and its read alone on resident masks; numpy's encode alone; the device time of the four
 launches (events); the bytes each arm copies to the host and the run counts of the batch.
 
-    python tools/predict_bench.py --rle [--out profiles/rle.md]"""
+    python tools/predict_bench.py --rle [--out profiles/rle.md]
+
+`--smooth` measures the mask smoothing (evalpost.Smooth: open, close, fill holes; csrc/morph.hip, csrc/evalpost.hip) on the same batch:
+the whole `predict` call with and without the spec, masks="host" followed by scipy.ndimage per mask on the host (the route the spec
+replaces), and the device time of `smooth_batch` alone on resident masks.
+
+    python tools/predict_bench.py --smooth [--radius 2] [--out profiles/smooth.md]"""
 import argparse
 import io
 import os
@@ -296,18 +302,117 @@ def rle_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, desc
         f.write(text)
 
 
+def smooth_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs):
+    """--smooth: open + close + fill holes at r = a.radius on the batch's masks: the device time alone on resident masks, the whole
+    `predict` call with and without the spec, and the host route the spec replaces (masks="host", then scipy.ndimage per mask)"""
+    try:
+        from scipy import ndimage
+    except ImportError:
+        ndimage = None
+    K, r = len(descs), a.radius
+    probs0 = evalpost.sigmoid_upsample(logits, SIZE, SIZE)
+    thr = float(probs0.median()) if a.thr is None else a.thr
+    spec = evalpost.Smooth(open=r, close=r, fill_holes=True)
+    pr = predict.Predictor(runner, pipe, thr=thr)
+
+    def call(masks, smooth=None):
+        return [p for x in pr.predict(files, exprs, images_per_batch=IMAGES, masks=masks, smooth=smooth) for p in x]
+
+    sq = np.ones((2 * r + 1, 2 * r + 1), bool)
+
+    def scipy_masks(masks):
+        out = []
+        for m in masks:
+            m = ndimage.binary_opening(m != 0, structure=sq)
+            m = ndimage.binary_erosion(ndimage.binary_dilation(m, structure=sq), structure=sq, border_value=1)
+            out.append(ndimage.binary_fill_holes(m))
+        return out
+
+    def host_smooth():
+        return scipy_masks([p.mask for p in call("host")])
+
+    st = evalpost.EvalStaging(dev, mask_bytes=16).pack_sizes(shapes, descs).upload()
+    src = torch.empty(st.out_bytes, dtype=torch.uint8, device=dev)
+    evalpost.predict_batch(probs0, st, evalpost.new_predict_stats(K, dev), 0, thr, out_masks=src)
+    out = torch.empty_like(src)
+    info = torch.zeros(K, 4, dtype=torch.int64, device=dev)
+    labels = torch.empty(st.out_bytes, dtype=torch.int32, device=dev)
+    work, fwork = evalpost.morph_work(st, dev), evalpost.fill_work(st, dev)
+
+    def device_only():
+        out.copy_(src)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        evalpost.smooth_batch(out, st, spec, info, 0, labels=labels, work=work, fwork=fwork)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    host_masks = [p.mask for p in call("host")]
+    smoothed = call("host", spec)
+    same = "scipy not installed: not compared" if ndimage is None else str(all(
+        np.array_equal(p.mask != 0, m) for p, m in zip(smoothed, scipy_masks(host_masks))))
+    changed = sum(int(((p.mask != 0) != (m != 0)).sum()) for p, m in zip(smoothed, host_masks))
+    arms = [lambda: call(None), lambda: call(None, spec), lambda: call("host"), lambda: call("host", spec)]
+    if ndimage is not None:
+        arms += [host_smooth, lambda: scipy_masks(host_masks)]
+    for f in arms:
+        timed(f, 2)
+    t = [[] for _ in arms]
+    dev_ms = []
+    for _ in range(ROUNDS):
+        for f, acc in zip(arms, t):
+            acc.append(timed(f, a.reps) * 1e3)
+        dev_ms.append(statistics.median(device_only() for _ in range(a.reps)))
+
+    def row(name, v):
+        return "| %s | %s | %.3f | %.3f | %.3f ms |" % (name, " ".join("%.3f" % x for x in v), min(v), max(v), statistics.median(v))
+
+    missing = "| %s | not measured (scipy is not installed) | | | |"
+    lines = ["# Mask smoothing in predict: open, close and fill holes on the device against scipy on the host", "",
+             "`python tools/predict_bench.py --smooth --radius %d --reps %d` on %s: R50, %dx%d, synthetic weights; %d synthetic 480x640"
+             % (r, a.reps, torch.cuda.get_device_name(0), SIZE, SIZE, IMAGES),
+             "JPEGs x %d expressions = %d masks per call, thr %.4f (the batch's median probability unless --thr), %s; %d rounds with the"
+             % (EXPRS, K, thr, spec, ROUNDS),
+             "arms interleaved, %d calls per round and arm; host clocks around work that ends with its results on the host, except the" % a.reps,
+             "device-time row (events around the launches of `smooth_batch`: pack, four row and four column passes, store; label, memset,",
+             "count, fill - masks resident).", "",
+             "| arm | rounds | min | max | median |", "|---|---|---|---|---|",
+             row("whole `Predictor.predict`, masks=None, no spec, ms per call", t[0]),
+             row("whole `Predictor.predict`, masks=None, smooth", t[1]),
+             row("whole `Predictor.predict`, masks=\"host\", no spec", t[2]),
+             row("whole `Predictor.predict`, masks=\"host\", smooth", t[3]),
+             row("whole `Predictor.predict`, masks=\"host\", then scipy.ndimage per mask on the host (the route replaced)", t[4])
+             if ndimage is not None else missing % "masks=\"host\", then scipy.ndimage per mask on the host (the route replaced)",
+             row("masks on the host: scipy.ndimage opening, closing, fill_holes per mask, ms per %d masks" % K, t[5])
+             if ndimage is not None else missing % "scipy.ndimage alone",
+             row("device time of `smooth_batch` alone (events), ms per %d masks" % K, dev_ms), "",
+             "The device's masks equal scipy's (binary_opening; binary_dilation then binary_erosion with border_value=1; binary_fill_holes): %s."
+             % same,
+             "The smoothing changes %d pixels of the batch's %d masks; the spec also labels and filters (a pass-all `Components`) so that"
+             % (changed, K),
+             "area, box and score are those of the final pixels - that is part of the smooth arms.", ""]
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None, help="default: profiles/predict.md, with --components profiles/components_bench.md, with --rle profiles/rle.md")
     ap.add_argument("--rle", action="store_true", help="measure the run-length mask output instead")
     ap.add_argument("--components", action="store_true", help="measure the connected-component clean-up instead")
+    ap.add_argument("--smooth", action="store_true", help="measure the mask smoothing (open, close, fill holes) instead")
+    ap.add_argument("--radius", type=int, default=2, help="--smooth only: the radius of the opening and of the closing")
     ap.add_argument("--keep", choices=evalpost.Components.KEEP, default="largest")
     ap.add_argument("--min-area", type=int, default=0)
     ap.add_argument("--connectivity", type=int, choices=(4, 8), default=8)
-    ap.add_argument("--thr", type=float, default=None, help="--components / --rle only: the threshold (default: the batch's median probability)")
+    ap.add_argument("--thr", type=float, default=None, help="--components / --rle / --smooth only: the threshold (default: the batch's median probability)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "components_bench.md" if a.components else "rle.md" if a.rle else "predict.md")
+    a.out = a.out or os.path.join(ROOT, "profiles", "components_bench.md" if a.components else "rle.md" if a.rle else "smooth.md" if a.smooth else "predict.md")
     if not torch.cuda.is_available():
         raise SystemExit("predict_bench needs a GPU (nothing here is measured on the CPU)")
     dev = torch.device("cuda:0")
@@ -332,6 +437,8 @@ def main():
         return components_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
     if a.rle:
         return rle_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
+    if a.smooth:
+        return smooth_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
     ring, turn = [evalpost.EvalStaging(dev, mask_bytes=16) for _ in range(3)], [0]
     K = len(descs)
 
