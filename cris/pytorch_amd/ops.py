@@ -1060,6 +1060,10 @@ class AdamTable:
                     dstF, dstD, N, Cin, ptaps, Cpad, Npad, transposed = pk
                     assert ptaps in (1, 9), "packed weights have 1 or 9 taps"
                     assert d.taps == ptaps or (d.taps == 0 and ptaps == 1), "a 9-tap packed weight takes its gradient in the GEMM layout"
+                    # adam_pack_tile reads a transposed weight's gradient [c][n] like the parameter, and the descriptor has one
+                    # cpad for the gradient's rows and the F pack's
+                    assert not (transposed and d.taps > 0), "a transposed packed weight takes its gradient in the parameter layout"
+                    assert d.taps == 0 or d.cpad == Cpad, "a GEMM-layout gradient and the F pack of its weight share one Cpad"
                     d.dstF, d.dstD = ptr(dstF), ptr(dstD)
                     d.N, d.cin, d.cpad, d.npad, d.transposed = N, Cin, Cpad, Npad, int(transposed)
                     d.ldF = dstF.shape[1] if dstF is not None else 0       # (row strides of the packs: ops.pack_row_stride)

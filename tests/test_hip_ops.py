@@ -1135,6 +1135,9 @@ def test_quickgelu_castdrop_axpy():
 
 
 def test_adam_matches_torch():
+    """three steps against torch.optim.Adam by whole-tensor relative L2: the anchor of the mode-equals-mode comparisons of the other
+    Adam tests.  Every element of p', m' and v' of one step, at block, tile and table edges and under guards, is checked in
+    tests/test_adam_edges.py (bounds and cases: tests/adam_edge_cases.py; their CPU twin: tests/test_adam_edges_cpu.py)."""
     ps = [rnd(1000), rnd(33, 7, seed=1), rnd(20000, seed=2)]
     gs = [rnd(*p.shape, seed=5) for p in ps]
     dev_p = [p.clone().to(DEV) for p in ps]
