@@ -22,6 +22,8 @@ binary masks come out at the original sizes and (area, score, bounding box) accu
 component / drop the small ones in place, statistics over the kept pixels, three launches) and `mask_iou_batch` (intersection /
 union counts from mask bytes) - DESIGN.md 9b.
 
+`polygon_count_batch` / `polygon_collect` end the same chain with polygons instead (polygon.py; csrc/polygon.hip): the corner
+visits are counted on the device, the host reads the totals, the rings are traced there and only their vertices cross to the host.
 `rle_encode_batch` / `rle_collect` are the last stage of that chain: the packed masks, filtered or not, become COCO run-length
 encodings (rle.py) - the transition positions are found on the device (csrc/rle.hip, four launches), only they cross to the host,
 and the strings of a batch are built there in one vectorised pass.
@@ -459,6 +461,101 @@ def rle_collect(runs, totals, descs, masks_u8=None, work=None):
             raise RuntimeError("rle_collect: the masks changed between the two encodes (%d positions, then %d)" % (need, int(t[n])))
     words = runs[:need].cpu().numpy().view(np.uint32)
     return rle.strings_from_positions(words, t[:n], [(descs.descs[i].h_out, descs.descs[i].w_out) for i in range(n)])
+
+
+POLYGON_RB, POLYGON_CG, POLYGON_CHUNK = 32, 64, 1024  # vertex rows of a band / vertex columns of a tile / visits per scan block in csrc/polygon.hip
+
+
+def polygon_work(descs, device, out=None):
+    """the scratch of `polygon_count_batch` for this batch (per-segment counts of both lists, one base per descriptor): `out` when
+    it is large enough, a new int64 buffer otherwise.  Nothing has to be zeroed; `polygon_collect` reads what the count left."""
+    words = (hip.load().cris_polygon_work_bytes(C.addressof(descs.descs), descs.n) + 7) // 8
+    if out is not None and out.numel() >= words:
+        return out
+    return torch.empty(words + words // 4, dtype=torch.int64, device=device)
+
+
+class PolygonBuffers:
+    """the grow-only device buffers of `polygon_collect`, reused across batches: trace_work (the tracer's scratch) and out (header,
+    ring table and vertices of a batch, one int64 buffer so that one copy reads them).  After a collect: `spans` = the int64 words
+    the trace was told it may use (trace_work, out), `table` / `vertices` = what the host read (int64 [rings, 4], int32 [V, 2])."""
+
+    def __init__(self, trace_work=None, out=None):
+        self.trace_work, self.out = trace_work, out
+        self.spans = self.table = self.vertices = None
+
+    @staticmethod
+    def _grown(buf, words, device):
+        if buf is not None and (buf.dtype != torch.int64 or buf.dim() != 1 or not buf.is_contiguous() or buf.device != device):
+            raise ValueError("polygon_collect: buffers must hold contiguous int64 buffers on the masks' device")
+        return buf if buf is not None and buf.numel() >= words else torch.empty(words + words // 4, dtype=torch.int64, device=device)
+
+
+def polygon_count_batch(masks_u8, descs, work=None):
+    """The vertices of every descriptor's mask in the packed buffer `masks_u8` as polygon rings (polygon.py states the format;
+    `descs`: the uploaded EvalStaging of the launch that wrote the masks) -> totals, int64 [n + 1] on the device: vertices per
+    descriptor and, last, their sum.  work: scratch from `polygon_work`; hand the same buffer to `polygon_collect`, which reads the
+    offsets this call leaves in it.  Three launches on the current stream (cris_polygon_count), none depending on the content;
+    nothing is synchronised or read here."""
+    _check_packed("polygon_count_batch", masks_u8, descs)
+    if descs.n < 1:
+        raise ValueError("polygon_count_batch: no descriptors")
+    work = polygon_work(descs, masks_u8.device, work)
+    totals = torch.empty(descs.n + 1, dtype=torch.int64, device=masks_u8.device)
+    hip.call("cris_polygon_count", ptr(masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), descs.n, ptr(work),
+             8 * work.numel(), ptr(totals), _stream())
+    return totals
+
+
+def polygon_collect(masks_u8, descs, totals, work=None, buffers=None, extra_rounds=0):
+    """The read of `polygon_count_batch` and the trace between its two copies -> list of polygon dicts per descriptor
+    ({"size": [h, w], "rings": [int32 [k, 2]], "holes": [bool]}, polygon.py).  First copy: totals.  Then the buffers are sized from
+    them (`buffers`: a PolygonBuffers to reuse, grown only when a batch needs more), cris_polygon_trace runs on the current stream
+    with ceil(log2(max vertices of a mask)) + extra_rounds jumping rounds, and the second copy reads the header, the ring table and
+    exactly totals[n] vertices.  masks_u8 and work: what the count read and left (work=None counts once more into a new scratch).
+    A batch without foreground issues no trace and no second copy."""
+    from . import polygon
+    _check_packed("polygon_collect", masks_u8, descs)
+    n = descs.n
+    if totals.dtype != torch.int64 or totals.shape != (n + 1,) or totals.device != masks_u8.device:
+        raise ValueError("polygon_collect: totals must be the int64 [n + 1] tensor of polygon_count_batch for these descriptors")
+    if buffers is not None and not isinstance(buffers, PolygonBuffers):
+        raise ValueError("polygon_collect: buffers must be an evalpost.PolygonBuffers, got %r" % (buffers,))
+    if isinstance(extra_rounds, bool) or not isinstance(extra_rounds, int) or not 0 <= extra_rounds <= 8:
+        raise ValueError("polygon_collect: extra_rounds must be an int in 0 .. 8, got %r" % (extra_rounds,))
+    if work is None:
+        work = polygon_work(descs, masks_u8.device)
+        totals = polygon_count_batch(masks_u8, descs, work=work)
+    elif work.dtype != torch.int64 or not work.is_contiguous() or work.device != masks_u8.device:
+        raise ValueError("polygon_collect: work must be the int64 scratch polygon_count_batch used")
+    buffers = PolygonBuffers() if buffers is None else buffers
+    sizes = [(descs.descs[i].h_out, descs.descs[i].w_out) for i in range(n)]
+    t = totals.cpu().numpy()                                               # the first copy
+    need = int(t[n])
+    if need != int(t[:n].sum()) or int(t[:n].min()) < 0 or (t[:n] & 1).any() or need > 2 ** 30:
+        raise RuntimeError("polygon_collect: totals %r do not belong to these %d descriptors" % (t.tolist()[:8], n))
+    buffers.spans = buffers.table = buffers.vertices = None
+    if need == 0:
+        return polygon.from_rings(np.zeros((0, 2), np.int32), np.zeros((0, 4), np.int64), sizes)
+    lib = hip.load()
+    ring_cap = need // 4
+    tw_words = (lib.cris_polygon_trace_work_bytes(need, n) + 7) // 8
+    out_words = 2 + 4 * ring_cap + need
+    buffers.trace_work = PolygonBuffers._grown(buffers.trace_work, tw_words, masks_u8.device)
+    buffers.out = PolygonBuffers._grown(buffers.out, out_words, masks_u8.device)
+    buffers.spans = (tw_words, out_words)
+    out = buffers.out
+    hip.call("cris_polygon_trace", ptr(masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), n, ptr(work),
+             8 * work.numel(), ptr(totals), need, int(t[:n].max()), extra_rounds, ptr(buffers.trace_work), 8 * tw_words,
+             out.data_ptr() + 8 * (2 + 4 * ring_cap), need, out.data_ptr() + 16, ring_cap, out.data_ptr(), _stream())
+    words = out[:out_words].cpu().numpy()                                  # the second copy
+    rings, written = int(words[0]), int(words[1])
+    if not 0 < rings <= ring_cap or written != need:
+        raise RuntimeError("polygon_collect: the trace found %d rings of %d vertices, the count %d vertices: the masks or the work "
+                           "buffer changed between the two calls" % (rings, written, need))
+    buffers.table = words[2:2 + 4 * rings].reshape(rings, 4)
+    buffers.vertices = words[2 + 4 * ring_cap:].view(np.int32).reshape(need, 2)
+    return polygon.from_rings(buffers.vertices, buffers.table, sizes)
 
 
 def mask_iou_batch(pred_masks_u8, descs, gt_masks_u8, counts, row0):

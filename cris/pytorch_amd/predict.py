@@ -22,21 +22,24 @@ hole filling: DESIGN.md 9b), before the clean-up; area, box and score are then t
 
 `masks="rle"` ends that chain on the device too: the masks of a batch stay in an internal device buffer, `evalpost.rle_encode_batch`
 finds their run-length transitions (csrc/rle.hip) and `Prediction.mask` is the COCO RLE dict of rle.py - a few hundred bytes per
-mask cross to the host instead of the image-sized mask.  `coco_results` turns such a result into the list a results file holds.
+mask cross to the host instead of the image-sized mask.  `masks="polygon"` does the same with polygons: `evalpost.polygon_count_batch`
+/ `polygon_collect` trace the rings of every mask there (csrc/polygon.hip) and `Prediction.mask` is the polygon dict of polygon.py,
+exact stair-step rings of pixel corners.  `coco_results` turns either result into the list a results file holds.
 
     python -m cris.pytorch_amd.predict --weights CKPT --config YAML --image F --expr "the left one" --out-prefix P [--keep largest]
-                                       [--rle-json RESULTS.json] [--open R] [--close R] [--fill-holes] [--max-hole-area N]
+                                       [--rle-json RESULTS.json] [--polygon-json RESULTS.json] [--open R] [--close R] [--fill-holes] [--max-hole-area N]
 """
 from collections import namedtuple
 
 import numpy as np
 import torch
 
-from . import evalpost, rle
+from . import evalpost, polygon, rle
 
 Prediction = namedtuple("Prediction", "sentence mask area box score")
 Prediction.__doc__ = """sentence: the expression; mask: uint8 [h, w] of 0 / 255 at the image's own size (numpy array, CUDA tensor view, None
-or with masks="rle" the COCO RLE dict {"size": [h, w], "counts": bytes} of that mask: `masks`); area: pixels above the threshold;
+with masks="rle" the COCO RLE dict {"size": [h, w], "counts": bytes} of that mask, or with masks="polygon" its polygon dict
+{"size", "rings", "holes"} of polygon.py: `masks`); area: pixels above the threshold;
 box: (x0, y0, x1, y1) half-open, None when area == 0; score: the mean warped
 probability over those pixels, score_q16 / (65536 * area) in float64 (each pixel's value rounded to 1 / 65536), 0.0 when area == 0"""
 
@@ -51,6 +54,7 @@ one; index: image (within the batch) of every expression, padded to a multiple o
 (inverse or None, image within the batch, probability map, statistics row of the WHOLE call) per real expression"""
 
 MASK_MODES = ("host", "device", "rle", None)
+POLYGON_MODE = "polygon"    # the mode whose masks come back as polygon dicts (polygon.py); every other mode is in MASK_MODES
 
 
 def _pad_to(n, multiple):
@@ -98,8 +102,8 @@ def _check_smooth(value, default):
 
 def _check_inputs(images, expressions, images_per_batch, masks):
     """-> (kind 'bytes' / 'array', expressions as lists); everything here is host-only"""
-    if masks not in MASK_MODES:
-        raise ValueError("predict: masks must be 'host', 'device', 'rle' or None, got %r" % (masks,))
+    if masks not in MASK_MODES and not (isinstance(masks, str) and masks == POLYGON_MODE):
+        raise ValueError("predict: masks must be 'host', 'device', 'rle' or None, or 'polygon', got %r" % (masks,))
     if int(images_per_batch) < 1:
         raise ValueError("predict: images_per_batch must be positive")
     images, expressions = list(images), list(expressions)
@@ -151,6 +155,7 @@ class Predictor:
         self._cc_masks = self._cc_labels = self._cc_work = None       # component clean-up scratch, reused across batches
         self._rle_runs = self._rle_work = None                        # run-length encoder buffers, reused across batches
         self._sm_work = None                                          # smoothing scratch (two bit planes), reused across batches
+        self._pg_work = self._pg_buffers = None                       # polygon tracer buffers, reused across batches (masks="polygon" only)
 
     def _staging(self):
         if self._ring is None:          # (the first device allocation: after every argument check)
@@ -173,6 +178,15 @@ class Predictor:
         runs, totals = evalpost.rle_encode_batch(out, st, runs=self._rle_runs, work=self._rle_work)
         return evalpost.rle_collect(runs, totals, st, masks_u8=out, work=self._rle_work)
 
+    def _trace_polygons(self, st, out):
+        """the batch's masks in `out` as polygon dicts: the count on the stream, the read of its totals, the trace sized from them
+        and the read of the vertices and the ring table (evalpost.polygon_collect); no trace for a batch without foreground"""
+        if self._pg_buffers is None:
+            self._pg_buffers = evalpost.PolygonBuffers()
+        self._pg_work = evalpost.polygon_work(st, self.device, self._pg_work)
+        totals = evalpost.polygon_count_batch(out, st, work=self._pg_work)
+        return evalpost.polygon_collect(out, st, totals, work=self._pg_work, buffers=self._pg_buffers)
+
     def _component_buffers(self, st, out):
         """the mask buffer of a batch that is cleaned up (out=None: an internal one that never leaves the device) and the label /
         work scratch, grown when a batch needs more and reused otherwise"""
@@ -189,7 +203,8 @@ class Predictor:
         back turned by their EXIF orientation, as cv2.imdecode returns them).  expressions: per image a str or a non-empty list
         of str.  masks: "host" (numpy arrays, one device-to-host copy per batch), "device" (views of one CUDA buffer per batch),
         "rle" (COCO run-length dicts, rle.py: the masks stay in an internal device buffer, are encoded there after any clean-up,
-        and only the run positions are copied) or None (statistics only: no mask buffer is allocated).  Returns a list per image
+        and only the run positions are copied), "polygon" (polygon dicts, polygon.py: the same internal buffer, traced there after
+        any clean-up, and only the ring vertices are copied) or None (statistics only: no mask buffer is allocated).  Returns a list per image
         of Prediction per expression.
         components: an evalpost.Components, None (no clean-up) or "default" (the constructor's).  With a spec every mask is
         labelled and filtered on the device before anything is read, the statistics are those of the kept pixels and the entries
@@ -198,7 +213,7 @@ class Predictor:
         and has its holes filled in place on the device (in that order) right after the threshold, then labelled and filtered
         (`components`, or a filter that keeps everything): the entries are ComponentPrediction whose area, box and score are those
         of the pixels finally set - filled pixels count with their own probability, whatever the threshold - n_components counts the
-        components of the smoothed mask and raw_area is the thresholded area before any of it; masks="rle" encodes the final mask;
+        components of the smoothed mask and raw_area is the thresholded area before any of it; masks="rle" / "polygon" encode the final mask;
         `smooth_info` holds the [total, 2] holes and pixels filled per expression."""
         from . import jpegdec
         spec = _check_components(components, self.components)
@@ -233,9 +248,9 @@ class Predictor:
             else:
                 logits = self.model(img[torch.tensor(b.index, device=self.device)], word)
             probs = evalpost.sigmoid_upsample(logits, img.shape[-2], img.shape[-1])
-            as_rle = masks == "rle"
-            out = None if masks is None or as_rle else torch.empty(st.out_bytes, dtype=torch.uint8, device=self.device)
-            if as_rle and spec is None:
+            as_rle, as_polygon = masks == "rle", masks == "polygon"
+            out = None if masks is None or as_rle or as_polygon else torch.empty(st.out_bytes, dtype=torch.uint8, device=self.device)
+            if (as_rle or as_polygon) and spec is None:
                 out = self._mask_buffer(st)
             if spec is not None:
                 out = self._component_buffers(st, out)
@@ -252,6 +267,9 @@ class Predictor:
                 continue
             if as_rle:
                 kept += self._encode_rle(st, out)
+                continue
+            if as_polygon:
+                kept += self._trace_polygons(st, out)[:K]
                 continue
             buf = out.cpu().numpy() if masks == "host" else out        # the batch's masks: one copy
             for k in range(K):
@@ -300,9 +318,10 @@ class Predictor:
 
 
 def coco_results(out, image_ids, expressions=True):
-    """The entries of a COCO-style results file from what `predict(..., masks="rle")` returned: out[i][j] belongs to image_ids[i].
-    Per expression {"image_id", "sentence" (left out with expressions=False), "segmentation": the RLE with str counts (goes
-    straight into json.dump), "bbox": [x, y, w, h] (COCO's form of Prediction.box; zeros for an empty mask), "area", "score"}.
+    """The entries of a COCO-style results file from what `predict(..., masks="rle")` or `masks="polygon"` returned: out[i][j]
+    belongs to image_ids[i].  Per expression {"image_id", "sentence" (left out with expressions=False), "segmentation": the RLE
+    with str counts, or for polygon results COCO's list of flat [x0, y0, x1, y1, ...] outer rings (polygon.to_coco: COCO polygons
+    cannot express holes; either goes straight into json.dump), "bbox": [x, y, w, h] (COCO's form of Prediction.box; zeros for an empty mask), "area", "score"}.
     Host only."""
     out, image_ids = list(out), list(image_ids)
     if len(out) != len(image_ids):
@@ -313,7 +332,8 @@ def coco_results(out, image_ids, expressions=True):
             if not isinstance(p.mask, dict):
                 raise ValueError("coco_results needs a result of predict(..., masks='rle'), got a mask of type %s" % type(p.mask).__name__)
             x0, y0, x1, y1 = p.box if p.box is not None else (0, 0, 0, 0)
-            entry = {"image_id": image_id, "sentence": p.sentence, "segmentation": rle.to_json(p.mask),
+            segmentation = polygon.to_coco(p.mask) if "rings" in p.mask else rle.to_json(p.mask)
+            entry = {"image_id": image_id, "sentence": p.sentence, "segmentation": segmentation,
                      "bbox": [int(x0), int(y0), int(x1 - x0), int(y1 - y0)], "area": int(p.area), "score": float(p.score)}
             if not expressions:
                 del entry["sentence"]
@@ -362,10 +382,12 @@ def main(argv=None):
     ap.add_argument("--config", help="the yaml the model was trained with (not needed with --synthetic)")
     ap.add_argument("--image", required=True, help="a JPEG file, or any image file Pillow opens")
     ap.add_argument("--expr", action="append", required=True, help="a referring expression; repeat for several")
-    ap.add_argument("--out-prefix", help="write PREFIX_<j>.png per expression (required unless --rle-json is given)")
+    ap.add_argument("--out-prefix", help="write PREFIX_<j>.png per expression (required unless --rle-json or --polygon-json is given)")
     ap.add_argument("--rle-json", metavar="PATH", help="write the COCO-style results list (RLE segmentation, bbox, area, score per "
                     "expression) to PATH; the masks are encoded on the GPU")
-    ap.add_argument("--image-id", default=None, help="the image_id of the --rle-json entries (default: the image's file name)")
+    ap.add_argument("--polygon-json", metavar="PATH", help="write the COCO-style results list with polygon segmentation (outer rings "
+                    "as flat vertex lists, bbox, area, score per expression) to PATH; the masks are traced on the GPU")
+    ap.add_argument("--image-id", default=None, help="the image_id of the --rle-json / --polygon-json entries (default: the image's file name)")
     ap.add_argument("--thr", type=float, default=0.35)
     ap.add_argument("--synthetic", nargs="?", const="r50", default=None, metavar="SPEC",
                     help="arch.synthetic_state_dict of r50 (default), r101 or tiny instead of --weights / --config")
@@ -384,8 +406,8 @@ def main(argv=None):
         smooth = evalpost.Smooth(a.open, a.close, a.fill_holes, a.max_hole_area)
     except ValueError as e:
         ap.error(str(e))
-    if not a.out_prefix and not a.rle_json:
-        ap.error("one of --out-prefix and --rle-json is required")
+    if not a.out_prefix and not a.rle_json and not a.polygon_json:
+        ap.error("one of --out-prefix, --rle-json and --polygon-json is required")
     if not torch.cuda.is_available():
         raise SystemExit("predict needs a GPU (there is no CPU fallback)")
     dev = torch.device("cuda:0")
@@ -419,8 +441,18 @@ def main(argv=None):
         with open(a.rle_json, "w") as f:
             json.dump(coco_results(encoded, [a.image_id if a.image_id is not None else os.path.basename(a.image)]), f)
         print("%s\t%d expressions\t%d bytes of RLE" % (a.rle_json, len(encoded[0]), sum(len(p.mask["counts"]) for p in encoded[0])))
-        if not a.out_prefix:
+        if not a.out_prefix and not a.polygon_json:
             return encoded[0]
+    if a.polygon_json:
+        import json
+        traced = predictor.predict([image], [a.expr], images_per_batch=1, masks="polygon")
+        os.makedirs(os.path.dirname(os.path.abspath(a.polygon_json)), exist_ok=True)
+        with open(a.polygon_json, "w") as f:
+            json.dump(coco_results(traced, [a.image_id if a.image_id is not None else os.path.basename(a.image)]), f)
+        print("%s\t%d expressions\t%d rings of %d vertices" % (a.polygon_json, len(traced[0]), sum(len(p.mask["rings"]) for p in traced[0]),
+                                                             sum(len(r) for p in traced[0] for r in p.mask["rings"])))
+        if not a.out_prefix:
+            return traced[0]
     out = predictor.predict([image], [a.expr], images_per_batch=1, masks="host")[0]
     os.makedirs(os.path.dirname(os.path.abspath(a.out_prefix)), exist_ok=True)
     for j, p in enumerate(out):

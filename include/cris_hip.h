@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_rle_encode / cris_rle_work_bytes (COCO run-length encoding of the packed masks on the device) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/rle.hip), every other launcher keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_erode_masks / cris_boundary_iou_batch / cris_boundary_work_bytes (square-structuring-element erosion of the packed masks and the Boundary IoU counts built on it) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/morph.hip), the radii travel as a separate int32 array, every other launcher keeps its signature, its kernel and its results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_morph_masks / cris_fill_holes / cris_fill_holes_work_bytes (mask smoothing: chained dilation / erosion of the packed masks, hence opening and closing, and hole filling) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc, the operation codes and radii travel as separate int32 arrays, cris_erode_masks / cris_boundary_iou_batch / cris_label_components / cris_filter_components keep their signatures, their launches and their results, and a binding that knows the three binds them at load, so a library without them is refused there */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_rle_encode / cris_rle_work_bytes (COCO run-length encoding of the packed masks on the device) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/rle.hip), every other launcher keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_erode_masks / cris_boundary_iou_batch / cris_boundary_work_bytes (square-structuring-element erosion of the packed masks and the Boundary IoU counts built on it) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/morph.hip), the radii travel as a separate int32 array, every other launcher keeps its signature, its kernel and its results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_morph_masks / cris_fill_holes / cris_fill_holes_work_bytes (mask smoothing: chained dilation / erosion of the packed masks, hence opening and closing, and hole filling) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc, the operation codes and radii travel as separate int32 arrays, cris_erode_masks / cris_boundary_iou_batch / cris_label_components / cris_filter_components keep their signatures, their launches and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_polygon_count / cris_polygon_trace / cris_polygon_work_bytes / cris_polygon_trace_work_bytes (polygon tracing of the packed masks on the device) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/polygon.hip), cris_rle_encode and every other launcher keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -603,6 +603,36 @@ int cris_mask_iou_batch(const unsigned char* pred, size_t pred_bytes, const cris
 size_t cris_rle_work_bytes(const cris_eval_desc* descs_host, int n);
 int cris_rle_encode(const unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev, int n,
                     void* work, size_t work_bytes, unsigned* runs, size_t run_words, long long* totals, void* stream);
+/* Polygon tracing of the same packed masks (csrc/polygon.hip, csrc/polygon_core.h; DESIGN.md 9b; the format: polygon.py).  Foreground
+ * as above: byte != 0 and x < w_out, the pitch padding is never read, outside the image is background.  Vertices are pixel corners
+ * (x, y), 0 <= x <= w_out, 0 <= y <= h_out; a crack is a unit edge between foreground and background directed with the foreground on
+ * its right (y grows downwards); a ring continues with the first existing crack among turn right, straight, turn left, and lists the
+ * vertices at which its direction changes, from its raster-first vertex on (outer rings leave it heading east, 2 A > 0; holes heading
+ * south, 2 A < 0).  The vertex count is data, hence two calls with a read of totals between them:
+ *   cris_polygon_count  totals (device, n + 1 words): totals[i] = vertices of descriptor i (always even), totals[n] = their sum.  work:
+ *     device scratch of cris_polygon_work_bytes(descs_host, n) bytes (per descriptor max over the batch of (h_out + 1) * ceil((w_out + 1) / 64)
+ *     and of (w_out + 1) * ceil((h_out + 1) / 32) words for the per-segment counts of the row-major and column-major lists, then n 64-bit
+ *     bases; 0 for NULL descriptors or n outside 1 .. 65535); nothing has to be zeroed.  Three launches, none depending on the content.
+ *   cris_polygon_trace  the same masks, descriptors and work (unchanged since the count: it holds the offsets), the device totals, and
+ *     what the host read from them: total_vertices = totals[n] (even, 2 .. 2^30: a batch without foreground is not traced) and
+ *     max_vertices_per_mask = max totals[i], which fixes the pointer-jumping rounds ceil(log2(max)) + extra_rounds (extra_rounds in
+ *     0 .. 8 changes no word of the result).  trace_work: device scratch of cris_polygon_trace_work_bytes(total_vertices, n) bytes (nine
+ *     words per vertex, one 64-bit word per 1024 vertices; 0 for a total outside 1 .. 2^30).  vertices: int32 (x, y) pairs, vertex_cap
+ *     PAIRS; ring i of the batch (descriptor order, then raster order of the ring starts) occupies rings[4 i ..] = (descriptor, offset
+ *     in pairs, length, 2 A) with ring_cap ROWS; header[0] = rings, header[1] = vertices written.  total_vertices pairs and
+ *     total_vertices / 4 rows always suffice; nothing is written at or beyond either capacity, rows and vertices that do not fit are
+ *     dropped.  7 + rounds launches; integers only, no atomics: the same words on every run.
+ * Checked on the host before the first launch: operands non-NULL, n in 1 .. 65535, alignment (8 bytes; vertices 4), both work sizes,
+ * the scalars above, and per descriptor h_out, w_out >= 1, (h_out + 1) * (w_out + 1) <= 2^28, w_out <= pitch, pitch a multiple of 4,
+ * pitch * h_out < 2^31, out_off >= 0 and the rectangle inside mask_bytes (map, row and mask_off are ignored). */
+size_t cris_polygon_work_bytes(const cris_eval_desc* descs_host, int n);
+size_t cris_polygon_trace_work_bytes(long long total_vertices, int n);
+int cris_polygon_count(const unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev, int n,
+                       void* work, size_t work_bytes, long long* totals, void* stream);
+int cris_polygon_trace(const unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev, int n,
+                       const void* work, size_t work_bytes, const long long* totals, long long total_vertices, long long max_vertices_per_mask,
+                       int extra_rounds, void* trace_work, size_t trace_work_bytes, int* vertices, size_t vertex_cap, long long* rings,
+                       size_t ring_cap, long long* header, void* stream);
 /* Erosion by a (2 r + 1)-square of the same packed masks and the Boundary IoU counts built on it (csrc/morph.hip; DESIGN.md 9b).
  * Foreground as above: byte != 0 and x < w_out, the pitch padding is never read as a pixel; outside the image is background.  With
  * r = radii[i] >= 1 the radius of descriptor i (computed on the host: the device reads integers; radii_host is checked here,

@@ -30,8 +30,16 @@ launches (events); the bytes each arm copies to the host and the run counts of t
 the whole `predict` call with and without the spec, masks="host" followed by scipy.ndimage per mask on the host (the route the spec
 replaces), and the device time of `smooth_batch` alone on resident masks.
 
-    python tools/predict_bench.py --smooth [--radius 2] [--out profiles/smooth.md]"""
+    python tools/predict_bench.py --smooth [--radius 2] [--out profiles/smooth.md]
+
+`--polygon` measures the polygon mask output (masks="polygon": csrc/polygon.hip, polygon.py) on the batch and threshold rule of
+`--rle`: the whole `predict` call with masks=None, masks="host", masks="host" followed by `polygon.encode` per mask on the host (the
+route the mode replaces) and masks="polygon"; the count and the collect alone on resident masks; numpy's encode alone; the device
+time of the count's and of the trace's launches by events; vertices and rings per mask and the bytes copied to the host.
+
+    python tools/predict_bench.py --polygon [--out profiles/polygon.md]"""
 import argparse
+import ctypes as C
 import io
 import os
 import statistics
@@ -43,7 +51,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from cris.pytorch_amd import arch, evalpost, jpegdec, predict, records, tokenizer      # noqa: E402
+from cris.pytorch_amd import arch, evalpost, hip, jpegdec, predict, records, tokenizer      # noqa: E402
 from cris.pytorch_amd.infer import InferenceRunner      # noqa: E402
 
 SIZE, WORD_LEN, IMAGES, EXPRS, ROUNDS, THR = 416, 17, 8, 3, 5, 0.35
@@ -302,6 +310,109 @@ def rle_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, desc
         f.write(text)
 
 
+def polygon_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs):
+    from cris.pytorch_amd import polygon
+    K = len(descs)
+    probs0 = evalpost.sigmoid_upsample(logits, SIZE, SIZE)
+    thr = float(probs0.median()) if a.thr is None else a.thr
+    pr = predict.Predictor(runner, pipe, thr=thr)
+
+    def call(masks):
+        return [p for x in pr.predict(files, exprs, images_per_batch=IMAGES, masks=masks) for p in x]
+
+    def host_encode():
+        return [polygon.encode(p.mask) for p in call("host")]
+
+    def same_dicts(x, y):
+        return len(x) == len(y) and all(p["size"] == q["size"] and p["holes"] == q["holes"] and len(p["rings"]) == len(q["rings"])
+                                        and all((u == v).all() for u, v in zip(p["rings"], q["rings"])) for p, q in zip(x, y))
+
+    # the batch's masks resident on the device, for the tracer alone
+    st = evalpost.EvalStaging(dev, mask_bytes=16).pack_sizes(shapes, descs).upload()
+    out = torch.empty(st.out_bytes, dtype=torch.uint8, device=dev)
+    evalpost.predict_batch(probs0, st, evalpost.new_predict_stats(K, dev), 0, thr, out_masks=out)
+    work, bufs = evalpost.polygon_work(st, dev), evalpost.PolygonBuffers()
+    host_masks = [p.mask for p in call("host")]
+
+    def count_and_collect():
+        return evalpost.polygon_collect(out, st, evalpost.polygon_count_batch(out, st, work=work), work=work, buffers=bufs)
+
+    def device_only():
+        """events around the launches: the count, then (the totals known from the first collect) the trace into the same buffers"""
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        totals = evalpost.polygon_count_batch(out, st, work=work)
+        e[1].record()
+        tw_words, out_words = bufs.spans
+        rc = need // 4
+        hip.call("cris_polygon_trace", out.data_ptr(), st.out_bytes, C.addressof(st.descs), st.dev.data_ptr(), K, work.data_ptr(), 8 * work.numel(),
+                 totals.data_ptr(), need, most, 0, bufs.trace_work.data_ptr(), 8 * tw_words, bufs.out.data_ptr() + 8 * (2 + 4 * rc), need,
+                 bufs.out.data_ptr() + 16, rc, bufs.out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        e[2].record()
+        e[2].synchronize()
+        return e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2])
+
+    def numpy_only():
+        return [polygon.encode(m) for m in host_masks]
+
+    totals = evalpost.polygon_count_batch(out, st, work=work).cpu().numpy()
+    need, most = int(totals[K]), int(totals[:K].max())
+    traced = count_and_collect()
+    same = same_dicts([p.mask for p in call("polygon")], host_encode()) and same_dicts(traced, numpy_only())
+    rings = [len(p["rings"]) for p in traced]
+    arms = [lambda: call(None), lambda: call("host"), host_encode, lambda: call("polygon"), count_and_collect, numpy_only]
+    for f in arms:
+        timed(f, 2)
+    t = [[] for _ in arms]
+    count_ms, trace_ms = [], []
+    for _ in range(ROUNDS):
+        for f, acc in zip(arms, t):
+            acc.append(timed(f, a.reps) * 1e3)
+        ev = [device_only() for _ in range(a.reps)]
+        count_ms.append(statistics.median(v[0] for v in ev))
+        trace_ms.append(statistics.median(v[1] for v in ev))
+
+    def row(name, v, note=""):
+        return "| %s | %s | %.3f | %.3f | %.3f ms | %s |" % (name, " ".join("%.3f" % x for x in v), min(v), max(v), statistics.median(v), note)
+
+    table = K * 6 * 8
+    poly_bytes = (K + 1) * 8 + 8 * (2 + 4 * (need // 4) + need)
+    rounds = max(most - 1, 1).bit_length()
+    spread = max(t[2]) - min(t[2])
+    slower = statistics.median(t[3]) - statistics.median(t[2])
+    verdict = ("beats the host route" if slower < -spread else "is slower than the host route" if slower > spread
+               else "is not resolved against the host route (the difference lies inside that arm's spread)")
+    lines = ["# Polygon masks from predict: traced on the device against numpy on the host", "",
+             "`python tools/predict_bench.py --polygon --reps %d` on %s: R50, %dx%d, synthetic weights; %d synthetic 480x640 JPEGs x %d"
+             % (a.reps, torch.cuda.get_device_name(0), SIZE, SIZE, IMAGES, EXPRS),
+             "expressions = %d masks per call, thr %.4f (the batch's median probability unless --thr); %d rounds with the arms interleaved,"
+             % (K, thr, ROUNDS),
+             "%d calls per round and arm; host clocks around work that ends with its results on the host, except the two device-time rows"
+             % a.reps, "(events around the 3 launches of `cris_polygon_count` and the 7 + %d of `cris_polygon_trace`, masks resident)." % rounds, "",
+             "| arm | rounds | min | max | median | bytes to the host per call |", "|---|---|---|---|---|---|",
+             row("whole `Predictor.predict`, masks=None, ms per call", t[0], "%d (the table)" % table),
+             row("whole `Predictor.predict`, masks=\"host\"", t[1], "%d (the masks) + %d" % (st.out_bytes, table)),
+             row("whole `Predictor.predict`, masks=\"host\", then `polygon.encode` per mask on the host (the route replaced)", t[2], "%d + %d" % (st.out_bytes, table)),
+             row("whole `Predictor.predict`, masks=\"polygon\"", t[3], "%d (totals; header, ring table and vertices) + %d" % (poly_bytes, table)),
+             row("masks resident: `polygon_count_batch` + `polygon_collect` (launches, two copies, dicts), ms per %d masks" % K, t[4], "%d" % poly_bytes),
+             row("masks on the host: `polygon.encode` per mask (numpy), ms per %d masks" % K, t[5], "-"),
+             row("device time of `cris_polygon_count` alone (events)", count_ms, "-"),
+             row("device time of `cris_polygon_trace` alone (events)", trace_ms, "-"), "",
+             "The routes give equal polygon dicts: %s.  Vertices per mask: min %d, median %d, max %d; %d in the batch.  Rings per mask: min %d,"
+             % (same, int(totals[:K].min()), int(statistics.median(int(v) for v in totals[:K])), most, need, min(rings)),
+             "median %d, max %d; %d in the batch.  %d jumping rounds.  The second copy holds %d bytes against %d bytes of masks."
+             % (int(statistics.median(rings)), max(rings), sum(rings), rounds, poly_bytes - (K + 1) * 8, st.out_bytes), "",
+             "masks=\"polygon\" against the host-encode arm: median %+.3f ms; spread of the host-encode arm over its rounds %.3f ms:"
+             % (slower, spread), "the device route %s on this batch." % verdict, "",
+             "The masks=None and masks=\"host\" calls issue the library calls they issued before and allocate nothing new",
+             "(tests/test_polygon_gpu.py records the calls); against the parent commit they are measured in alternating processes, below", "when that was run.", ""]
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
 def smooth_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs):
     """--smooth: open + close + fill holes at r = a.radius on the batch's masks: the device time alone on resident masks, the whole
     `predict` call with and without the spec, and the host route the spec replaces (masks="host", then scipy.ndimage per mask)"""
@@ -404,15 +515,16 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None, help="default: profiles/predict.md, with --components profiles/components_bench.md, with --rle profiles/rle.md")
     ap.add_argument("--rle", action="store_true", help="measure the run-length mask output instead")
+    ap.add_argument("--polygon", action="store_true", help="measure the polygon mask output instead (writes profiles/polygon.md)")
     ap.add_argument("--components", action="store_true", help="measure the connected-component clean-up instead")
     ap.add_argument("--smooth", action="store_true", help="measure the mask smoothing (open, close, fill holes) instead")
     ap.add_argument("--radius", type=int, default=2, help="--smooth only: the radius of the opening and of the closing")
     ap.add_argument("--keep", choices=evalpost.Components.KEEP, default="largest")
     ap.add_argument("--min-area", type=int, default=0)
     ap.add_argument("--connectivity", type=int, choices=(4, 8), default=8)
-    ap.add_argument("--thr", type=float, default=None, help="--components / --rle / --smooth only: the threshold (default: the batch's median probability)")
+    ap.add_argument("--thr", type=float, default=None, help="--components / --rle / --polygon / --smooth only: the threshold (default: the batch's median probability)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "components_bench.md" if a.components else "rle.md" if a.rle else "smooth.md" if a.smooth else "predict.md")
+    a.out = a.out or os.path.join(ROOT, "profiles", "components_bench.md" if a.components else "rle.md" if a.rle else "polygon.md" if a.polygon else "smooth.md" if a.smooth else "predict.md")
     if not torch.cuda.is_available():
         raise SystemExit("predict_bench needs a GPU (nothing here is measured on the CPU)")
     dev = torch.device("cuda:0")
@@ -437,6 +549,8 @@ def main():
         return components_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
     if a.rle:
         return rle_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
+    if a.polygon:
+        return polygon_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
     if a.smooth:
         return smooth_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
     ring, turn = [evalpost.EvalStaging(dev, mask_bytes=16) for _ in range(3)], [0]
