@@ -464,6 +464,7 @@ def rle_collect(runs, totals, descs, masks_u8=None, work=None):
 
 
 POLYGON_RB, POLYGON_CG, POLYGON_CHUNK = 32, 64, 1024  # vertex rows of a band / vertex columns of a tile / visits per scan block in csrc/polygon.hip
+POLYGON_SIMPLIFY_WAVE, POLYGON_SIMPLIFY_LDS = 256, 4096  # longest ring one wave simplifies / longest ring staged in LDS (SP_WAVE_RING, SP_LDS_RING in csrc/simplify.hip)
 
 
 def polygon_work(descs, device, out=None):
@@ -478,11 +479,16 @@ def polygon_work(descs, device, out=None):
 class PolygonBuffers:
     """the grow-only device buffers of `polygon_collect`, reused across batches: trace_work (the tracer's scratch) and out (header,
     ring table and vertices of a batch, one int64 buffer so that one copy reads them).  After a collect: `spans` = the int64 words
-    the trace was told it may use (trace_work, out), `table` / `vertices` = what the host read (int64 [rings, 4], int32 [V, 2])."""
+    the trace was told it may use (trace_work, out), `table` / `vertices` = what the host read (int64 [rings, 4], int32 [V, 2]).
+    A collect with `simplify` also holds simplify_work (the simplifier's scratch) and simplified (its header of 4 words, ring table
+    and vertices): `spans` then has four entries (trace_work, out, simplify_work, simplified), `table` is int64 [rings, 5],
+    `vertices` the kept ones, and `header` the simplifier's (rings, vertices, traced rings, rounds of the deepest ring) followed by
+    the traced vertices."""
 
-    def __init__(self, trace_work=None, out=None):
+    def __init__(self, trace_work=None, out=None, simplify_work=None, simplified=None):
         self.trace_work, self.out = trace_work, out
-        self.spans = self.table = self.vertices = None
+        self.simplify_work, self.simplified = simplify_work, simplified
+        self.spans = self.table = self.vertices = self.header = None
 
     @staticmethod
     def _grown(buf, words, device):
@@ -507,14 +513,21 @@ def polygon_count_batch(masks_u8, descs, work=None):
     return totals
 
 
-def polygon_collect(masks_u8, descs, totals, work=None, buffers=None, extra_rounds=0):
+def polygon_collect(masks_u8, descs, totals, work=None, buffers=None, extra_rounds=0, simplify=None):
     """The read of `polygon_count_batch` and the trace between its two copies -> list of polygon dicts per descriptor
     ({"size": [h, w], "rings": [int32 [k, 2]], "holes": [bool]}, polygon.py).  First copy: totals.  Then the buffers are sized from
     them (`buffers`: a PolygonBuffers to reuse, grown only when a batch needs more), cris_polygon_trace runs on the current stream
     with ceil(log2(max vertices of a mask)) + extra_rounds jumping rounds, and the second copy reads the header, the ring table and
     exactly totals[n] vertices.  masks_u8 and work: what the count read and left (work=None counts once more into a new scratch).
-    A batch without foreground issues no trace and no second copy."""
+    A batch without foreground issues no trace and no second copy.
+    simplify: None, or the Douglas-Peucker tolerance in pixels (a multiple of 0.25 in [0.25, 64]; polygon.simplify states the
+    definition, every h_out and w_out must be <= 32767).  Then cris_polygon_simplify follows the trace on the stream - the host reads
+    nothing in between -, the buffers also hold its scratch and its output, and the dicts are the simplified ones (with "epsilon").
+    Instead of the traced header, table and vertices the host reads the simplifier's 4-word header and then exactly the simplified
+    table and vertices: one small extra copy, the header, for a second copy that no longer carries every stair-step corner.
+    simplify=None issues exactly the calls and allocations it did before there was a simplifier."""
     from . import polygon
+    q = None if simplify is None else polygon.check_epsilon(simplify)
     _check_packed("polygon_collect", masks_u8, descs)
     n = descs.n
     if totals.dtype != torch.int64 or totals.shape != (n + 1,) or totals.device != masks_u8.device:
@@ -523,19 +536,24 @@ def polygon_collect(masks_u8, descs, totals, work=None, buffers=None, extra_roun
         raise ValueError("polygon_collect: buffers must be an evalpost.PolygonBuffers, got %r" % (buffers,))
     if isinstance(extra_rounds, bool) or not isinstance(extra_rounds, int) or not 0 <= extra_rounds <= 8:
         raise ValueError("polygon_collect: extra_rounds must be an int in 0 .. 8, got %r" % (extra_rounds,))
+    sizes = [(descs.descs[i].h_out, descs.descs[i].w_out) for i in range(n)]
+    if q is not None:
+        for h, w in sizes:
+            polygon.check_simplify_size(h, w)
     if work is None:
         work = polygon_work(descs, masks_u8.device)
         totals = polygon_count_batch(masks_u8, descs, work=work)
     elif work.dtype != torch.int64 or not work.is_contiguous() or work.device != masks_u8.device:
         raise ValueError("polygon_collect: work must be the int64 scratch polygon_count_batch used")
     buffers = PolygonBuffers() if buffers is None else buffers
-    sizes = [(descs.descs[i].h_out, descs.descs[i].w_out) for i in range(n)]
     t = totals.cpu().numpy()                                               # the first copy
     need = int(t[n])
     if need != int(t[:n].sum()) or int(t[:n].min()) < 0 or (t[:n] & 1).any() or need > 2 ** 30:
         raise RuntimeError("polygon_collect: totals %r do not belong to these %d descriptors" % (t.tolist()[:8], n))
-    buffers.spans = buffers.table = buffers.vertices = None
+    buffers.spans = buffers.table = buffers.vertices = buffers.header = None
     if need == 0:
+        if q is not None:
+            return polygon.simplify_from_rings(np.zeros((0, 2), np.int32), np.zeros((0, 5), np.int64), sizes, simplify)
         return polygon.from_rings(np.zeros((0, 2), np.int32), np.zeros((0, 4), np.int64), sizes)
     lib = hip.load()
     ring_cap = need // 4
@@ -545,9 +563,33 @@ def polygon_collect(masks_u8, descs, totals, work=None, buffers=None, extra_roun
     buffers.out = PolygonBuffers._grown(buffers.out, out_words, masks_u8.device)
     buffers.spans = (tw_words, out_words)
     out = buffers.out
+    if q is not None:
+        sw_words = (lib.cris_polygon_simplify_work_bytes(need, ring_cap) + 7) // 8
+        so_words = 4 + 5 * ring_cap + need
+        buffers.simplify_work = PolygonBuffers._grown(buffers.simplify_work, sw_words, masks_u8.device)
+        buffers.simplified = PolygonBuffers._grown(buffers.simplified, so_words, masks_u8.device)
+        buffers.spans = (tw_words, out_words, sw_words, so_words)
     hip.call("cris_polygon_trace", ptr(masks_u8), descs.out_bytes, C.addressof(descs.descs), descs.dev.data_ptr(), n, ptr(work),
              8 * work.numel(), ptr(totals), need, int(t[:n].max()), extra_rounds, ptr(buffers.trace_work), 8 * tw_words,
              out.data_ptr() + 8 * (2 + 4 * ring_cap), need, out.data_ptr() + 16, ring_cap, out.data_ptr(), _stream())
+    if q is not None:
+        simp = buffers.simplified
+        hip.call("cris_polygon_simplify", out.data_ptr() + 8 * (2 + 4 * ring_cap), out.data_ptr() + 16, out.data_ptr(), need, ring_cap, q,
+                 C.addressof(descs.descs), n, ptr(buffers.simplify_work), 8 * sw_words, simp.data_ptr() + 8 * (4 + 5 * ring_cap), need,
+                 simp.data_ptr() + 32, ring_cap, simp.data_ptr(), _stream())
+        head = simp[:4].cpu().numpy()                                      # the small extra copy: the simplifier's header
+        rings, kept, traced = int(head[0]), int(head[1]), int(head[2])
+        if not (0 < traced <= ring_cap and 0 <= rings <= traced and 3 * rings <= kept <= need):
+            raise RuntimeError("polygon_collect: the simplifier left %d rings of %d vertices from %d traced rings of %d vertices: the "
+                               "masks or the work buffer changed between the calls" % (rings, kept, traced, need))
+        buffers.header = np.append(head, need)                             # ... and, last, the vertices the trace had delivered
+        if rings == 0:
+            buffers.table, buffers.vertices = np.zeros((0, 5), np.int64), np.zeros((0, 2), np.int32)
+        else:                                                              # the second copy: exactly the table and the kept vertices
+            words = torch.cat([simp[4:4 + 5 * rings], simp[4 + 5 * ring_cap:4 + 5 * ring_cap + kept]]).cpu().numpy()
+            buffers.table = words[:5 * rings].reshape(rings, 5)
+            buffers.vertices = words[5 * rings:].view(np.int32).reshape(kept, 2)    # an (x, y) pair is one 64-bit word
+        return polygon.simplify_from_rings(buffers.vertices, buffers.table, sizes, simplify)
     words = out[:out_words].cpu().numpy()                                  # the second copy
     rings, written = int(words[0]), int(words[1])
     if not 0 < rings <= ring_cap or written != need:

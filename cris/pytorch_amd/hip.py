@@ -369,6 +369,8 @@ _SIGS = {
     "cris_polygon_count": (I, [P, C.c_size_t, P, P, I, P, C.c_size_t, P, P]),
     "cris_polygon_trace": (I, [P, C.c_size_t, P, P, I, P, C.c_size_t, P, C.c_longlong, C.c_longlong, I, P, C.c_size_t, P, C.c_size_t, P,
                            C.c_size_t, P, P]),
+    "cris_polygon_simplify_work_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong]),
+    "cris_polygon_simplify": (I, [P, P, P, C.c_longlong, C.c_longlong, I, P, I, P, C.c_size_t, P, C.c_size_t, P, C.c_size_t, P, P]),
     "cris_boundary_work_bytes": (C.c_size_t, [P, I]),
     "cris_erode_masks": (I, [P, C.c_size_t, P, P, I, P, P, P, C.c_size_t, P, C.c_size_t, I, P]),
     "cris_boundary_iou_batch": (I, [P, C.c_size_t, P, P, I, P, C.c_size_t, P, P, P, C.c_size_t, P, I, P]),

@@ -27,7 +27,7 @@ mask cross to the host instead of the image-sized mask.  `masks="polygon"` does 
 exact stair-step rings of pixel corners.  `coco_results` turns either result into the list a results file holds.
 
     python -m cris.pytorch_amd.predict --weights CKPT --config YAML --image F --expr "the left one" --out-prefix P [--keep largest]
-                                       [--rle-json RESULTS.json] [--polygon-json RESULTS.json] [--open R] [--close R] [--fill-holes] [--max-hole-area N]
+                                       [--rle-json RESULTS.json] [--polygon-json RESULTS.json [--simplify EPS]] [--open R] [--close R] [--fill-holes] [--max-hole-area N]
 """
 from collections import namedtuple
 
@@ -100,6 +100,19 @@ def _check_smooth(value, default):
     return evalpost.smooth_spec(value, "predict: smooth")
 
 
+def _check_simplify(value, default, masks, where="predict"):
+    """the Douglas-Peucker tolerance of one call: "default" -> the constructor's, which applies to masks="polygon" alone; None ->
+    none; a value is checked (polygon.check_epsilon) and is valid only with masks="polygon".  Host only."""
+    if isinstance(value, str) and value == "default":
+        return default if isinstance(masks, str) and masks == POLYGON_MODE else None
+    if value is None:
+        return None
+    polygon.check_epsilon(value)
+    if not (isinstance(masks, str) and masks == POLYGON_MODE):
+        raise ValueError("%s: simplify is valid only with masks='polygon', got masks=%r" % (where, masks))
+    return float(value)
+
+
 def _check_inputs(images, expressions, images_per_batch, masks):
     """-> (kind 'bytes' / 'array', expressions as lists); everything here is host-only"""
     if masks not in MASK_MODES and not (isinstance(masks, str) and masks == POLYGON_MODE):
@@ -130,16 +143,18 @@ def _check_inputs(images, expressions, images_per_batch, masks):
 
 
 class Predictor:
-    """`Predictor(model, pipeline, thr=0.35, components=None, smooth=None)`: model - an InferenceRunner, the drop-in CRIS module in eval mode, or any callable
+    """`Predictor(model, pipeline, thr=0.35, components=None, smooth=None, simplify=None)`: model - an InferenceRunner, the drop-in CRIS module in eval mode, or any callable
     `(img, word) -> logits [B, 1, h, w]`; when it offers `segment(img, word, image_index)` or `segment_expressions`, the visual
     encoder runs once per image, otherwise `model(img[index], word)` is called.  pipeline - a RecordPipeline in mode "test" (its
     preprocessor, tokenizer, word length and decode threads are used; no record is needed).  components - None or an
     evalpost.Components: the mask clean-up `predict` applies unless the call names another.  smooth - None or an evalpost.Smooth:
-    the smoothing (open, close, fill holes) `predict` applies before that clean-up unless the call names another."""
+    the smoothing (open, close, fill holes) `predict` applies before that clean-up unless the call names another.  simplify - None
+    or the Douglas-Peucker tolerance in pixels (a multiple of 0.25 in [0.25, 64]) `predict` applies to masks="polygon" results
+    unless the call names another."""
 
     RING = 3            # descriptor staging buffers in flight (evaluate.Evaluator.RING)
 
-    def __init__(self, model, pipeline, thr=0.35, components=None, smooth=None):
+    def __init__(self, model, pipeline, thr=0.35, components=None, smooth=None, simplify=None):
         if getattr(pipeline, "mode", None) != "test":
             raise ValueError("Predictor needs a RecordPipeline in mode 'test', got %r" % (getattr(pipeline, "mode", None),))
         thr = float(thr)
@@ -148,7 +163,9 @@ class Predictor:
         self.model, self.pipe, self.thr = model, pipeline, thr
         self.components = evalpost.components_spec(components, "Predictor: components")
         self.smooth = evalpost.smooth_spec(smooth, "Predictor: smooth")
+        self.simplify = None if simplify is None else polygon.check_epsilon(simplify) / 4.0
         self.smooth_info = None                                       # after a call with a Smooth spec: [total, 2] holes, pixels filled
+        self.simplify_info = None                                     # after a call that simplified: (rings, vertices) traced, before the simplifier
         self.device = pipeline.device
         self._segment = getattr(model, "segment", None) or getattr(model, "segment_expressions", None)
         self._ring, self._turn = None, 0
@@ -178,14 +195,20 @@ class Predictor:
         runs, totals = evalpost.rle_encode_batch(out, st, runs=self._rle_runs, work=self._rle_work)
         return evalpost.rle_collect(runs, totals, st, masks_u8=out, work=self._rle_work)
 
-    def _trace_polygons(self, st, out):
+    def _trace_polygons(self, st, out, simplify=None):
         """the batch's masks in `out` as polygon dicts: the count on the stream, the read of its totals, the trace sized from them
-        and the read of the vertices and the ring table (evalpost.polygon_collect); no trace for a batch without foreground"""
+        and the read of the vertices and the ring table (evalpost.polygon_collect); no trace for a batch without foreground.
+        simplify: the tolerance of the simplifier that follows the trace on the device, or None"""
         if self._pg_buffers is None:
             self._pg_buffers = evalpost.PolygonBuffers()
         self._pg_work = evalpost.polygon_work(st, self.device, self._pg_work)
         totals = evalpost.polygon_count_batch(out, st, work=self._pg_work)
-        return evalpost.polygon_collect(out, st, totals, work=self._pg_work, buffers=self._pg_buffers)
+        if simplify is None:
+            return evalpost.polygon_collect(out, st, totals, work=self._pg_work, buffers=self._pg_buffers)
+        got = evalpost.polygon_collect(out, st, totals, work=self._pg_work, buffers=self._pg_buffers, simplify=simplify)
+        if self._pg_buffers.header is not None:                       # what the trace had found: the simplifier's header and the count's total
+            self.simplify_info = (self.simplify_info[0] + int(self._pg_buffers.header[2]), self.simplify_info[1] + int(self._pg_buffers.header[4]))
+        return got
 
     def _component_buffers(self, st, out):
         """the mask buffer of a batch that is cleaned up (out=None: an internal one that never leaves the device) and the label /
@@ -198,7 +221,7 @@ class Predictor:
         return out
 
     @torch.no_grad()
-    def predict(self, images, expressions, images_per_batch=8, masks="host", components="default", smooth="default"):
+    def predict(self, images, expressions, images_per_batch=8, masks="host", components="default", smooth="default", simplify="default"):
         """images: JPEG bytes per image, or uint8 RGB [h, w, 3] arrays / tensors per image (one kind per call; JPEG files come
         back turned by their EXIF orientation, as cv2.imdecode returns them).  expressions: per image a str or a non-empty list
         of str.  masks: "host" (numpy arrays, one device-to-host copy per batch), "device" (views of one CUDA buffer per batch),
@@ -214,13 +237,18 @@ class Predictor:
         (`components`, or a filter that keeps everything): the entries are ComponentPrediction whose area, box and score are those
         of the pixels finally set - filled pixels count with their own probability, whatever the threshold - n_components counts the
         components of the smoothed mask and raw_area is the thresholded area before any of it; masks="rle" / "polygon" encode the final mask;
-        `smooth_info` holds the [total, 2] holes and pixels filled per expression."""
+        `smooth_info` holds the [total, 2] holes and pixels filled per expression.
+        simplify: a Douglas-Peucker tolerance in pixels (a multiple of 0.25 in [0.25, 64]), None (exact stair-step rings) or
+        "default" (the constructor's, which applies to masks="polygon" alone).  Valid only with masks="polygon": the rings are
+        simplified on the device right after the trace (csrc/simplify.hip; polygon.simplify states the definition) and
+        `Prediction.mask` is the simplified dict {"size", "rings", "holes", "epsilon"}; area, box and score stay those of the mask itself."""
         from . import jpegdec
         spec = _check_components(components, self.components)
         sspec = _check_smooth(smooth, self.smooth)
         if sspec is not None and spec is None:
             spec = evalpost.Components()                               # keeps everything: labels, statistics of the final pixels
         kind, images, exprs = _check_inputs(images, expressions, images_per_batch, masks)
+        eps = _check_simplify(simplify, self.simplify, masks)
         images_per_batch = int(images_per_batch)
         plans = plan_predict([len(e) for e in exprs], images_per_batch)
         total = sum(len(e) for e in exprs)
@@ -230,6 +258,7 @@ class Predictor:
             info = torch.zeros(total, 4, dtype=torch.int64, device=self.device)
         sinfo = None if sspec is None else torch.zeros(total, 4, dtype=torch.int64, device=self.device)
         kept = []                                                      # per expression: its mask (or None)
+        self.simplify_info = None if eps is None else (0, 0)
         for b in plans:
             part = images[b.lo:b.lo + b.n]
             if kind == "bytes":
@@ -269,7 +298,7 @@ class Predictor:
                 kept += self._encode_rle(st, out)
                 continue
             if as_polygon:
-                kept += self._trace_polygons(st, out)[:K]
+                kept += self._trace_polygons(st, out, eps)[:K]
                 continue
             buf = out.cpu().numpy() if masks == "host" else out        # the batch's masks: one copy
             for k in range(K):
@@ -387,6 +416,8 @@ def main(argv=None):
                     "expression) to PATH; the masks are encoded on the GPU")
     ap.add_argument("--polygon-json", metavar="PATH", help="write the COCO-style results list with polygon segmentation (outer rings "
                     "as flat vertex lists, bbox, area, score per expression) to PATH; the masks are traced on the GPU")
+    ap.add_argument("--simplify", type=float, default=None, metavar="EPS", help="simplify the polygons of --polygon-json on the GPU (Douglas-Peucker, "
+                    "tolerance EPS pixels: a multiple of 0.25 in [0.25, 64])")
     ap.add_argument("--image-id", default=None, help="the image_id of the --rle-json / --polygon-json entries (default: the image's file name)")
     ap.add_argument("--thr", type=float, default=0.35)
     ap.add_argument("--synthetic", nargs="?", const="r50", default=None, metavar="SPEC",
@@ -408,6 +439,13 @@ def main(argv=None):
         ap.error(str(e))
     if not a.out_prefix and not a.rle_json and not a.polygon_json:
         ap.error("one of --out-prefix, --rle-json and --polygon-json is required")
+    if a.simplify is not None:
+        if not a.polygon_json:
+            ap.error("--simplify is valid only with --polygon-json")
+        try:
+            polygon.check_epsilon(a.simplify)
+        except ValueError as e:
+            ap.error(str(e))
     if not torch.cuda.is_available():
         raise SystemExit("predict needs a GPU (there is no CPU fallback)")
     dev = torch.device("cuda:0")
@@ -445,12 +483,17 @@ def main(argv=None):
             return encoded[0]
     if a.polygon_json:
         import json
-        traced = predictor.predict([image], [a.expr], images_per_batch=1, masks="polygon")
+        traced = predictor.predict([image], [a.expr], images_per_batch=1, masks="polygon", simplify=a.simplify)
         os.makedirs(os.path.dirname(os.path.abspath(a.polygon_json)), exist_ok=True)
         with open(a.polygon_json, "w") as f:
             json.dump(coco_results(traced, [a.image_id if a.image_id is not None else os.path.basename(a.image)]), f)
-        print("%s\t%d expressions\t%d rings of %d vertices" % (a.polygon_json, len(traced[0]), sum(len(p.mask["rings"]) for p in traced[0]),
-                                                             sum(len(r) for p in traced[0] for r in p.mask["rings"])))
+        nrings, nverts = sum(len(p.mask["rings"]) for p in traced[0]), sum(len(r) for p in traced[0] for r in p.mask["rings"])
+        if a.simplify is None:
+            print("%s\t%d expressions\t%d rings of %d vertices" % (a.polygon_json, len(traced[0]), nrings, nverts))
+        else:
+            before = predictor.simplify_info
+            print("%s\t%d expressions\tepsilon %g\t%d rings of %d vertices before\t%d rings of %d vertices after"
+                  % (a.polygon_json, len(traced[0]), a.simplify, before[0], before[1], nrings, nverts))
         if not a.out_prefix:
             return traced[0]
     out = predictor.predict([image], [a.expr], images_per_batch=1, masks="host")[0]

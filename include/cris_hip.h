@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_rle_encode / cris_rle_work_bytes (COCO run-length encoding of the packed masks on the device) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/rle.hip), every other launcher keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_erode_masks / cris_boundary_iou_batch / cris_boundary_work_bytes (square-structuring-element erosion of the packed masks and the Boundary IoU counts built on it) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/morph.hip), the radii travel as a separate int32 array, every other launcher keeps its signature, its kernel and its results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_morph_masks / cris_fill_holes / cris_fill_holes_work_bytes (mask smoothing: chained dilation / erosion of the packed masks, hence opening and closing, and hole filling) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc, the operation codes and radii travel as separate int32 arrays, cris_erode_masks / cris_boundary_iou_batch / cris_label_components / cris_filter_components keep their signatures, their launches and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_polygon_count / cris_polygon_trace / cris_polygon_work_bytes / cris_polygon_trace_work_bytes (polygon tracing of the packed masks on the device) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/polygon.hip), cris_rle_encode and every other launcher keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_rle_encode / cris_rle_work_bytes (COCO run-length encoding of the packed masks on the device) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/rle.hip), every other launcher keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_erode_masks / cris_boundary_iou_batch / cris_boundary_work_bytes (square-structuring-element erosion of the packed masks and the Boundary IoU counts built on it) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/morph.hip), the radii travel as a separate int32 array, every other launcher keeps its signature, its kernel and its results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_morph_masks / cris_fill_holes / cris_fill_holes_work_bytes (mask smoothing: chained dilation / erosion of the packed masks, hence opening and closing, and hole filling) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc, the operation codes and radii travel as separate int32 arrays, cris_erode_masks / cris_boundary_iou_batch / cris_label_components / cris_filter_components keep their signatures, their launches and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_polygon_count / cris_polygon_trace / cris_polygon_work_bytes / cris_polygon_trace_work_bytes (polygon tracing of the packed masks on the device) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/polygon.hip), cris_rle_encode and every other launcher keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_polygon_simplify / cris_polygon_simplify_work_bytes (Douglas-Peucker simplification of the traced rings on the device) were added at 8 without moving it in the same way: two new symbols in a translation unit of their own (csrc/simplify.hip) that read what cris_polygon_trace left, cris_polygon_count / cris_polygon_trace keep their signatures, their launches and their results, and a binding that knows the two binds them at load, so a library without them is refused there */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -633,6 +633,25 @@ int cris_polygon_trace(const unsigned char* masks, size_t mask_bytes, const cris
                        const void* work, size_t work_bytes, const long long* totals, long long total_vertices, long long max_vertices_per_mask,
                        int extra_rounds, void* trace_work, size_t trace_work_bytes, int* vertices, size_t vertex_cap, long long* rings,
                        size_t ring_cap, long long* header, void* stream);
+/* Douglas-Peucker simplification of the rings cris_polygon_trace left on the device (csrc/simplify.hip, csrc/simplify_core.h; DESIGN.md
+ * 9b; polygon.simplify is the host restatement).  q = 4 epsilon in 1 .. 256 (epsilon in pixels, a multiple of 0.25 in [0.25, 64]).  Per
+ * ring v_0 .. v_k-1 (v_k = v_0): the kept set starts as {0, a}, a the smallest index that maximises |v_i - v_0|^2; for a segment (i, j) of
+ * kept vertices with j - i >= 2 the candidate is the m in (i, j) of greatest c_m = |(v_j - v_i) x (v_m - v_i)|, among equals the one
+ * nearest the middle (smallest |2 m - (i + j)|), among those the smallest m; it is kept, and both halves go on, iff
+ * 16 c_m^2 > q^2 |v_j - v_i|^2, strictly.  All of it in 64-bit integers, which bounds h_out, w_out <= 32767.  A ring left with fewer than
+ * 3 vertices is removed.  vertices, rings (4 words per row) and header: the trace's outputs, only read, nothing is read by the host in
+ * between; total_vertices: the pairs `vertices` holds (what the trace was given), ring_cap: the rows `rings` holds.  work: device scratch
+ * of cris_polygon_simplify_work_bytes(total_vertices, ring_cap) bytes (0 for a total outside 4 .. 2^30 or a ring_cap outside 1 .. 2^28);
+ * nothing has to be zeroed.  out_vertices: the kept (x, y) pairs of the remaining rings in ring order, out_vertex_cap PAIRS
+ * (>= total_vertices); out_rings: 5 words per remaining ring = (descriptor, offset in pairs, length, 2 A of the simplified ring - it may be
+ * 0 or odd -, 1 iff the TRACED ring is a hole), out_ring_cap ROWS (>= ring_cap); out_header[0 .. 4) = rings, vertices written, traced
+ * rings, rounds of the deepest ring.  3 or 4 launches; integers only, the same words on every run.  Checked on the host before the
+ * first launch: operands non-NULL, alignment (8 bytes; vertices 4), q, the scalars, the capacities, the work size, n in 1 .. 65535 and per
+ * descriptor h_out, w_out in 1 .. 32767 (nothing else of a descriptor is read). */
+size_t cris_polygon_simplify_work_bytes(long long total_vertices, long long ring_cap);
+int cris_polygon_simplify(const int* vertices, const long long* rings, const long long* header, long long total_vertices, long long ring_cap,
+                          int q, const cris_eval_desc* descs_host, int n, void* work, size_t work_bytes, int* out_vertices,
+                          size_t out_vertex_cap, long long* out_rings, size_t out_ring_cap, long long* out_header, void* stream);
 /* Erosion by a (2 r + 1)-square of the same packed masks and the Boundary IoU counts built on it (csrc/morph.hip; DESIGN.md 9b).
  * Foreground as above: byte != 0 and x < w_out, the pitch padding is never read as a pixel; outside the image is background.  With
  * r = radii[i] >= 1 the radius of descriptor i (computed on the host: the device reads integers; radii_host is checked here,

@@ -37,7 +37,17 @@ replaces), and the device time of `smooth_batch` alone on resident masks.
 route the mode replaces) and masks="polygon"; the count and the collect alone on resident masks; numpy's encode alone; the device
 time of the count's and of the trace's launches by events; vertices and rings per mask and the bytes copied to the host.
 
-    python tools/predict_bench.py --polygon [--out profiles/polygon.md]"""
+    python tools/predict_bench.py --polygon [--out profiles/polygon.md]
+
+`--simplify EPS` measures the Douglas-Peucker simplifier of those polygons (csrc/simplify.hip, polygon.simplify) on the same batch and
+threshold rule: the device time of its launches by events on resident rings, the whole `predict` call with masks="polygon" with and
+without simplify=EPS, the route it replaces (masks="polygon", then `polygon.simplify` per mask on the host), the bytes copied,
+vertices and rings before and after, the rounds of the deepest ring and the IoU of decode(simplified) against the exact mask.
+`--polygon-call` times nothing but the whole masks="polygon" call and prints one JSON line: run from this tree and from a checkout of
+the parent commit in alternating processes, it is the comparison of the unsimplified path the profile ends with.
+
+    python tools/predict_bench.py --simplify 1 [--out profiles/polygon_simplify.md]
+    python tools/predict_bench.py --polygon-call [--package-root ../parent-checkout]"""
 import argparse
 import ctypes as C
 import io
@@ -50,7 +60,8 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# --package-root DIR: import the package from another built checkout (the parent commit's, for --polygon-call)
+sys.path.insert(0, next((sys.argv[i + 1] for i, v in enumerate(sys.argv[:-1]) if v == "--package-root"), ROOT))
 from cris.pytorch_amd import arch, evalpost, hip, jpegdec, predict, records, tokenizer      # noqa: E402
 from cris.pytorch_amd.infer import InferenceRunner      # noqa: E402
 
@@ -413,6 +424,129 @@ def polygon_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, 
         f.write(text)
 
 
+def polygon_call_arm(a, dev, files, exprs, pipe, runner, logits):
+    """--polygon-call: the whole predict call with masks="polygon" (no simplify) alone, one JSON line - for alternating processes of
+    this tree and of the parent commit, whose copy of this file has no such arm: it is run from this copy with --package-root"""
+    import json
+    probs0 = evalpost.sigmoid_upsample(logits, SIZE, SIZE)
+    thr = float(probs0.median()) if a.thr is None else a.thr
+    pr = predict.Predictor(runner, pipe, thr=thr)
+    call = lambda: pr.predict(files, exprs, images_per_batch=IMAGES, masks="polygon")      # noqa: E731
+    timed(call, 3)
+    rounds = [round(timed(call, a.reps) * 1e3, 3) for _ in range(ROUNDS)]
+    print(json.dumps({"arm": "masks=polygon", "package": os.path.dirname(os.path.abspath(predict.__file__)), "thr": round(thr, 4), "rounds_ms": rounds,
+                      "median_ms": statistics.median(rounds), "vertices": sum(len(r) for x in call() for p in x for r in p.mask["rings"])}))
+
+
+def simplify_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs):
+    """--simplify EPS: see the module docstring"""
+    from cris.pytorch_amd import polygon
+    eps, q = float(a.simplify), polygon.check_epsilon(a.simplify)
+    K = len(descs)
+    probs0 = evalpost.sigmoid_upsample(logits, SIZE, SIZE)
+    thr = float(probs0.median()) if a.thr is None else a.thr
+    pr = predict.Predictor(runner, pipe, thr=thr)
+
+    def call(simplify=None):
+        return [p for x in pr.predict(files, exprs, images_per_batch=IMAGES, masks="polygon", simplify=simplify) for p in x]
+
+    def host_simplify():
+        return [polygon.simplify(p.mask, eps) for p in call()]
+
+    def same_dicts(x, y):
+        return len(x) == len(y) and all(p["size"] == q["size"] and p["holes"] == q["holes"] and len(p["rings"]) == len(q["rings"]) and p["epsilon"] == q["epsilon"]
+                                        and all(u.shape == v.shape and (u == v).all() for u, v in zip(p["rings"], q["rings"])) for p, q in zip(x, y))
+
+    # the batch's rings resident on the device, for the simplifier alone
+    st = evalpost.EvalStaging(dev, mask_bytes=16).pack_sizes(shapes, descs).upload()
+    out = torch.empty(st.out_bytes, dtype=torch.uint8, device=dev)
+    evalpost.predict_batch(probs0, st, evalpost.new_predict_stats(K, dev), 0, thr, out_masks=out)
+    work, bufs = evalpost.polygon_work(st, dev), evalpost.PolygonBuffers()
+    totals = evalpost.polygon_count_batch(out, st, work=work)
+    resident = evalpost.polygon_collect(out, st, totals, work=work, buffers=bufs, simplify=eps)
+    header = [int(v) for v in bufs.header]
+    need, ring_cap = header[4], header[4] // 4
+    _, _, sw_words, so_words = bufs.spans
+
+    def device_only():
+        """events around the simplifier's launches on the traced rings the collect above left in the buffers"""
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        o, sp = bufs.out, bufs.simplified
+        e[0].record()
+        hip.call("cris_polygon_simplify", o.data_ptr() + 8 * (2 + 4 * ring_cap), o.data_ptr() + 16, o.data_ptr(), need, ring_cap, q, C.addressof(st.descs), K,
+                 bufs.simplify_work.data_ptr(), 8 * sw_words, sp.data_ptr() + 8 * (4 + 5 * ring_cap), need, sp.data_ptr() + 32, ring_cap, sp.data_ptr(),
+                 torch.cuda.current_stream().cuda_stream)
+        e[1].record()
+        e[1].synchronize()
+        return e[0].elapsed_time(e[1])
+
+    exact = [p.mask for p in call()]
+    host_only = lambda: [polygon.simplify(p, eps) for p in exact]          # noqa: E731
+    simplified = [p.mask for p in call(eps)]
+    same = same_dicts(simplified, host_simplify()) and same_dicts(resident, host_only())
+    ious = []
+    for p, s in zip(exact, simplified):
+        m, d = polygon.decode(p) != 0, polygon.decode(s) != 0
+        ious.append(float((m & d).sum()) / float((m | d).sum()) if (m | d).any() else 1.0)
+    arms = [lambda: call(), lambda: call(eps), host_simplify, host_only]
+    for f in arms:
+        timed(f, 2)
+    t = [[] for _ in arms]
+    dev_ms = []
+    for _ in range(ROUNDS):
+        for f, acc in zip(arms, t):
+            acc.append(timed(f, a.reps) * 1e3)
+        dev_ms.append(statistics.median(device_only() for _ in range(a.reps)))
+
+    def row(name, v, note=""):
+        return "| %s | %s | %.3f | %.3f | %.3f ms | %s |" % (name, " ".join("%.3f" % x for x in v), min(v), max(v), statistics.median(v), note)
+
+    def verdict(diff, spread, what):
+        return ("is faster than %s" % what if diff < -spread else "is slower than %s" % what if diff > spread
+                else "is not resolved against %s (the difference lies inside that arm's spread)" % what)
+
+    table = K * 6 * 8
+    before_v, before_r = [sum(len(r) for r in p["rings"]) for p in exact], [len(p["rings"]) for p in exact]
+    after_v, after_r = [sum(len(r) for r in p["rings"]) for p in simplified], [len(p["rings"]) for p in simplified]
+    poly_bytes = (K + 1) * 8 + 8 * (2 + 4 * ring_cap + need)
+    simp_bytes = (K + 1) * 8 + 8 * 4 + 8 * (5 * header[0] + header[1])
+    d_plain, s_plain = statistics.median(t[1]) - statistics.median(t[0]), max(t[0]) - min(t[0])
+    d_host, s_host = statistics.median(t[1]) - statistics.median(t[2]), max(t[2]) - min(t[2])
+    launches = 4 if need > evalpost.POLYGON_SIMPLIFY_WAVE else 3
+    lines = ["# Simplified polygons from predict: Douglas-Peucker on the device against numpy on the host", "",
+             "`python tools/predict_bench.py --simplify %g --reps %d` on %s: R50, %dx%d, synthetic weights; %d synthetic 480x640 JPEGs x %d"
+             % (eps, a.reps, torch.cuda.get_device_name(0), SIZE, SIZE, IMAGES, EXPRS),
+             "expressions = %d masks per call, thr %.4f (the batch's median probability unless --thr), epsilon %g pixels; %d rounds with the arms"
+             % (K, thr, eps, ROUNDS),
+             "interleaved, %d calls per round and arm; host clocks around work that ends with its results on the host, except the device-time row"
+             % a.reps, "(events around the %d launches of `cris_polygon_simplify`, the traced rings resident)." % launches, "",
+             "| arm | rounds | min | max | median | bytes to the host per call |", "|---|---|---|---|---|---|",
+             row("whole `Predictor.predict`, masks=\"polygon\", ms per call", t[0], "%d (totals; header, ring table and vertices) + %d (the table)" % (poly_bytes, table)),
+             row("whole `Predictor.predict`, masks=\"polygon\", simplify=%g" % eps, t[1], "%d (totals; header; simplified table and vertices) + %d" % (simp_bytes, table)),
+             row("whole `Predictor.predict`, masks=\"polygon\", then `polygon.simplify` per mask on the host (the route replaced)", t[2], "%d + %d" % (poly_bytes, table)),
+             row("polygons on the host: `polygon.simplify` per mask (numpy), ms per %d masks" % K, t[3], "-"),
+             row("device time of `cris_polygon_simplify` alone (events)", dev_ms, "-"), "",
+             "The routes give equal simplified dicts: %s.  Vertices per mask before: min %d, median %d, max %d, %d in the batch; after: min %d,"
+             % (same, min(before_v), int(statistics.median(before_v)), max(before_v), sum(before_v), min(after_v)),
+             "median %d, max %d, %d in the batch.  Rings per mask before: min %d, median %d, max %d, %d in the batch; after: min %d, median %d,"
+             % (int(statistics.median(after_v)), max(after_v), sum(after_v), min(before_r), int(statistics.median(before_r)), max(before_r), sum(before_r),
+                min(after_r), int(statistics.median(after_r))),
+             "max %d, %d in the batch.  The deepest ring took %d rounds.  IoU of decode(simplified) against the exact mask: min %.4f, median %.4f,"
+             % (max(after_r), sum(after_r), header[3], min(ious), statistics.median(ious)),
+             "max %.4f." % max(ious), "",
+             "simplify=%g against the unsimplified call: median %+.3f ms; spread of the unsimplified arm over its rounds %.3f ms: the simplified call"
+             % (eps, d_plain, s_plain), "%s." % verdict(d_plain, s_plain, "the unsimplified one"),
+             "simplify=%g against the host route: median %+.3f ms; spread of the host-route arm %.3f ms: the device route %s on this batch."
+             % (eps, d_host, s_host, verdict(d_host, s_host, "the host route")), "",
+             "masks=\"polygon\" without simplify issues the library calls it issued before and allocates nothing new (tests/test_polygon_simplify_gpu.py",
+             "records the calls); against the parent commit it is measured in alternating processes, below when that was run.", ""]
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
 def smooth_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs):
     """--smooth: open + close + fill holes at r = a.radius on the batch's masks: the device time alone on resident masks, the whole
     `predict` call with and without the spec, and the host route the spec replaces (masks="host", then scipy.ndimage per mask)"""
@@ -516,6 +650,10 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/predict.md, with --components profiles/components_bench.md, with --rle profiles/rle.md")
     ap.add_argument("--rle", action="store_true", help="measure the run-length mask output instead")
     ap.add_argument("--polygon", action="store_true", help="measure the polygon mask output instead (writes profiles/polygon.md)")
+    ap.add_argument("--simplify", type=float, default=None, metavar="EPS", help="measure the Douglas-Peucker simplifier of the polygon output at this "
+                    "tolerance instead (writes profiles/polygon_simplify.md)")
+    ap.add_argument("--polygon-call", action="store_true", help="time the whole masks=\"polygon\" call alone and print one JSON line")
+    ap.add_argument("--package-root", default=None, metavar="DIR", help="import cris.pytorch_amd from this built checkout instead of this tree")
     ap.add_argument("--components", action="store_true", help="measure the connected-component clean-up instead")
     ap.add_argument("--smooth", action="store_true", help="measure the mask smoothing (open, close, fill holes) instead")
     ap.add_argument("--radius", type=int, default=2, help="--smooth only: the radius of the opening and of the closing")
@@ -524,7 +662,7 @@ def main():
     ap.add_argument("--connectivity", type=int, choices=(4, 8), default=8)
     ap.add_argument("--thr", type=float, default=None, help="--components / --rle / --polygon / --smooth only: the threshold (default: the batch's median probability)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "components_bench.md" if a.components else "rle.md" if a.rle else "polygon.md" if a.polygon else "smooth.md" if a.smooth else "predict.md")
+    a.out = a.out or os.path.join(ROOT, "profiles", "components_bench.md" if a.components else "rle.md" if a.rle else "polygon.md" if a.polygon else "polygon_simplify.md" if a.simplify is not None else "smooth.md" if a.smooth else "predict.md")
     if not torch.cuda.is_available():
         raise SystemExit("predict_bench needs a GPU (nothing here is measured on the CPU)")
     dev = torch.device("cuda:0")
@@ -549,6 +687,10 @@ def main():
         return components_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
     if a.rle:
         return rle_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
+    if a.polygon_call:
+        return polygon_call_arm(a, dev, files, exprs, pipe, runner, logits)
+    if a.simplify is not None:
+        return simplify_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
     if a.polygon:
         return polygon_arm(a, dev, files, exprs, pipe, runner, logits, invs, shapes, plan, descs)
     if a.smooth:
