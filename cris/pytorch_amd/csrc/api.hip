@@ -40,6 +40,7 @@ extern "C" int cris_sizeof(const char* name) {
     S(cris_zero_ranges);
     S(cris_sample_desc);
     S(cris_eval_desc);
+    S(cris_mask_src);
     S(cris_jpeg_info);
     S(cris_jpeg_image);
 #undef S

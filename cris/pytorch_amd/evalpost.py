@@ -37,7 +37,11 @@ csrc/morph.hip over 64-bit bit planes of the masks - DESIGN.md 9b.
 (fills pin-holes and narrow gaps) and hole filling, in that order.  `morph_batch` chains erosions and dilations of the packed masks
 over the same bit planes (`dilate_batch`, `open_batch`, `close_batch`; csrc/morph.hip cris_morph_masks), `fill_holes_batch` labels
 the background with the union-find of `label_components` and fills the components that do not reach the image's frame
-(csrc/evalpost.hip cris_fill_holes), `smooth_batch` applies a spec in place - DESIGN.md 9b."""
+(csrc/evalpost.hip cris_fill_holes), `smooth_batch` applies a spec in place - DESIGN.md 9b.
+
+`decode_masks_batch` is the inverse of the encoder and the tracer: RLE and polygon masks (`mask_form`, packed as `MaskSources`)
+are decoded on the device straight into either packed layout (csrc/decode.hip), so that encoded ground truth
+(`EvalStaging.pack_encoded` / `decode`) and results files (evaluate.score_results) run through the kernels above - DESIGN.md 9b."""
 import ctypes as C
 import math
 
@@ -177,9 +181,68 @@ class EvalStaging:
         self.n, self.mask_bytes, self.out_bytes = len(descs), 0, out_off
         return self
 
+    def pack_encoded(self, masks, descs):
+        """`pack` for a batch whose masks are, some or all, still encoded.  masks: `mask_form` results - "array" entries (PNG ground
+        truth decoded on the host) are packed as `pack` packs them, "rle" / "polygon" entries get a slot of the same shape ON THE DEVICE
+        ONLY: their mask-source table (hip.MaskSrc) and payload (`MaskSources`) follow the descriptor table in the part of the buffer
+        below mask_base, which grows like the descriptors' own part, and `decode()` fills the slots after `upload()`.  The slots of
+        the host-decoded masks come first, so that the one asynchronous copy still covers a prefix: descriptors, sources, payload and
+        those masks - without any, the tables and the payload only.  After upload() and decode(), `masks` holds in every slot what
+        `pack` of the host-decoded masks in that order (arrays first) would have uploaded.  descs: as for `pack`, the mask index
+        names an entry of `masks` in the caller's order."""
+        forms = list(masks)
+        order = [i for i, f in enumerate(forms) if f[0] == "array"] + [i for i, f in enumerate(forms) if f[0] != "array"]
+        shapes = [(f[1], f[2]) for f in forms]
+        pitches = [self._up(w, 4) for _, w in shapes]
+        offs, off, host_bytes = [0] * len(forms), 0, 0
+        for i in order:
+            offs[i] = off
+            off += self._up(pitches[i] * shapes[i][0], self.ALIGN)
+            if forms[i][0] == "array":
+                host_bytes = off
+        enc = [i for i in order if forms[i][0] != "array"]
+        srcs = MaskSources([forms[i] for i in enc], [(offs[i], pitches[i]) for i in enc]) if enc else None
+        aux_off = self._up(len(descs) * C.sizeof(hip.EvalDesc), self.ALIGN)
+        aux_end = aux_off + (0 if srcs is None else srcs.blob.size)
+        if aux_end > self.mask_base or off > self.mask_cap:
+            rows = max(-(-(aux_end + aux_end // 4) // C.sizeof(hip.EvalDesc)) if aux_end > self.mask_base else 0, len(descs), self.max_descs)
+            self._reserve(rows, max(off + off // 4 if off > self.mask_cap else 0, self.mask_cap))
+        self.wait()
+        for i in order[:len(forms) - len(enc)]:
+            (h, w), p, m = shapes[i], pitches[i], forms[i][3]
+            rows = self._bytes[self.mask_base + offs[i]:self.mask_base + offs[i] + p * h].reshape(h, p)
+            rows[:, :w] = m.numpy() if torch.is_tensor(m) else m
+            rows[:, w:] = 0
+        if srcs is not None:
+            self._bytes[aux_off:aux_end] = srcs.blob
+            srcs.place(self.host.data_ptr() + aux_off, None if self.dev is None else self.dev.data_ptr() + aux_off)
+        out_off = 0
+        for i, (mat, mi, mp, row) in enumerate(descs):
+            m = np.ascontiguousarray(np.asarray(mat, dtype=np.float64).reshape(6))
+            h, w = shapes[mi]
+            hip.call("cris_eval_desc_fill", C.addressof(self.descs[i]), m.ctypes.data_as(C.c_void_p), w, h, int(mp), offs[mi], pitches[mi],
+                     out_off, int(row))
+            out_off += self._up(pitches[mi] * h, self.ALIGN)
+        self.n, self.mask_bytes, self.out_bytes = len(descs), off, out_off
+        self._pending = (srcs, self.mask_base + host_bytes if host_bytes else aux_end)
+        return self
+
+    def decode(self, work=None):
+        """after `pack_encoded(...).upload()`: decode the encoded masks into their slots of `masks` on the current stream
+        (`decode_masks_batch`; nothing to do for a batch that `pack` packed).  work: scratch from `decode_work` to reuse -> the
+        scratch used, or `work` itself when there was nothing to decode."""
+        srcs = getattr(self, "encoded", None)
+        if srcs is None:
+            return work
+        work = decode_work(srcs, self.device, work)
+        decode_masks_batch(srcs, self.masks, work=work)
+        return work
+
     def upload(self):
-        """one asynchronous copy of the descriptor table and the masks (the used prefix of the buffer) on the current stream"""
-        end = self.mask_base + self.mask_bytes
+        """one asynchronous copy of the descriptor table and the masks (the used prefix of the buffer) on the current stream; after
+        `pack_encoded` the prefix ends with the last host-decoded mask, or with the payload when there is none"""
+        self.encoded, end = self.__dict__.pop("_pending", None) or (None, self.mask_base + self.mask_bytes)
+        self.last_upload_bytes = end
         self.dev[:end].copy_(self.host[:end], non_blocking=True)
         self.event = torch.cuda.Event()
         self.event.record()
@@ -923,3 +986,202 @@ def smooth_batch(masks_u8, descs, spec, info, row0, labels=None, work=None, fwor
         morph_batch(masks_u8, descs, spec.ops, out=masks_u8, work=work)
     if spec.fill_holes:
         fill_holes_batch(masks_u8, descs, info, row0, spec.hole_connectivity, spec.max_hole_area, labels=labels, work=fwork)
+
+
+# ---- encoded masks back onto the device: the inverse of rle_encode_batch and of polygon_count_batch / polygon_collect ----
+
+MASK_KINDS = ("array", "rle", "polygon")
+DECODE_T = 256          # threads of a block in csrc/decode.hip (the sizes at which its kernels take another chunk)
+
+
+def mask_form(mask, where="mask"):
+    """Any form a mask is exchanged in -> (kind, h, w, payload), validated on the host before anything else happens:
+        "array"    uint8 [h, w] array or CPU tensor (non-zero is foreground), or the bytes of an 8-bit gray PNG (decoded here);
+                   payload = the uint8 array / tensor
+        "rle"      {"size": [h, w], "counts": str | bytes | list of integers} (rle.py; str counts are what a results JSON holds);
+                   payload = the counts as int64
+        "polygon"  {"size", "rings", "holes"} with or without "epsilon" (polygon.py: traced or simplified); payload = the rings
+    An object with a `.mask` attribute (predict.Prediction) stands for that mask.  COCO's flat [x0, y0, x1, y1, ...] polygon lists
+    are NOT accepted: polygon.to_coco drops the holes and the "epsilon" marker, and COCO fills such lists as a union, not even-odd,
+    so they do not name one mask - exchange RLE (masks="rle") instead.  Raises ValueError (prefixed with `where`)."""
+    from . import pngdec, polygon, rle
+    if not isinstance(mask, (dict, np.ndarray, bytes, bytearray, memoryview, list)) and not torch.is_tensor(mask) and hasattr(mask, "mask"):
+        mask = mask.mask
+    try:
+        if isinstance(mask, (bytes, bytearray, memoryview)):
+            try:
+                mask = pngdec.decode_gray(bytes(mask))
+            except hip.HipLibraryError as e:
+                raise ValueError("bytes that are no 8-bit gray PNG (%s)" % e) from None
+        if torch.is_tensor(mask) or isinstance(mask, np.ndarray):
+            if mask.ndim != 2 or mask.dtype != (torch.uint8 if torch.is_tensor(mask) else np.uint8) or (torch.is_tensor(mask) and mask.device.type != "cpu"):
+                raise ValueError("an array mask must be uint8 [h, w] on the host, got %s %s" % (mask.dtype, tuple(mask.shape)))
+            return "array", int(mask.shape[0]), int(mask.shape[1]), mask
+        if isinstance(mask, dict) and "counts" in mask:
+            h, w, counts = rle._parts(mask)
+            return "rle", h, w, counts
+        if isinstance(mask, dict) and "rings" in mask:
+            h, w = polygon.validate(mask)
+            return "polygon", h, w, list(mask["rings"])
+        if isinstance(mask, (list, tuple)):
+            raise ValueError("COCO's flat polygon lists are not accepted (no holes, no even-odd rule): exchange RLE instead")
+        raise ValueError("expected a uint8 array, PNG bytes, an RLE dict or a polygon dict, got %r" % (type(mask).__name__,))
+    except ValueError as e:
+        raise ValueError("%s: %s" % (where, e)) from None
+
+
+def mask_to_array(form):
+    """the host decode of a `mask_form` result -> uint8 [h, w] numpy array of the mask's own values (array) or 0 / 255"""
+    from . import polygon, rle
+    kind, h, w, payload = form
+    if kind == "array":
+        return payload.numpy() if torch.is_tensor(payload) else payload
+    if kind == "rle":
+        return rle.decode({"size": [h, w], "counts": payload})
+    return polygon._decode_general(payload, h, w)
+
+
+class MaskSources:
+    """The tables of one decode call on the host, in ONE contiguous block of bytes (`blob`, uint8) so that one copy uploads them:
+    the mask-source table (hip.MaskSrc, one row per mask), the ring table (int64 [R, 3] of (mask, offset, length)), the vertices
+    (int32 [V, 2]) and the RLE counts (uint32), each section 8-byte aligned.  `place(host_address, device_address)` tells where the
+    block lies when a caller copied it elsewhere (EvalStaging); `upload(device)` makes a pinned copy and sends it with one
+    asynchronous copy.  n, n_rle, n_polygon: rows; out_bytes: the end of the farthest slot."""
+
+    def __init__(self, forms, slots):
+        """forms: `mask_form` results of kind "rle" / "polygon" with h, w >= 1; slots: (dst_off, pitch) per mask"""
+        from . import polygon, rle
+        forms, slots = list(forms), list(slots)
+        if len(forms) != len(slots) or not 1 <= len(forms) <= 65535:
+            raise ValueError("MaskSources: need one slot per mask and 1 .. 65535 masks, got %d masks, %d slots" % (len(forms), len(slots)))
+        counts, rings, verts, rows = [], [], [], []
+        n_counts = n_rings = n_verts = 0
+        self.out_bytes = 0
+        for i, ((kind, h, w, payload), (dst_off, pitch)) in enumerate(zip(forms, slots)):
+            dst_off, pitch = int(dst_off), int(pitch)
+            if kind not in ("rle", "polygon") or h < 1 or w < 1:
+                raise ValueError("MaskSources: mask %d must be an RLE or a polygon of positive size, got %r %d x %d" % (i, kind, h, w))
+            if h * w >= rle.MAX_PIXELS or (kind == "polygon" and (h + 1) * (w + 1) > polygon.MAX_VERTICES):
+                raise ValueError("MaskSources: mask %d is too large (%d x %d)" % (i, h, w))
+            if pitch < w or pitch % 4 or pitch * h >= 2 ** 31 or dst_off < 0 or dst_off % 4:
+                raise ValueError("MaskSources: slot %d needs a pitch that is a multiple of 4 and >= w and a non-negative offset that is "
+                                 "a multiple of 4, got offset %d pitch %d for %d x %d" % (i, dst_off, pitch, h, w))
+            self.out_bytes = max(self.out_bytes, dst_off + pitch * h)
+            if kind == "rle":
+                c = np.asarray(payload, np.int64)
+                rows.append((dst_off, n_counts, pitch, h, w, c.size, hip.MASK_RLE))
+                counts.append(c.astype(np.uint32))
+                n_counts += c.size
+            else:
+                rows.append((dst_off, n_rings, pitch, h, w, len(payload), hip.MASK_POLYGON))
+                for r in payload:
+                    rings.append((i, n_verts, r.shape[0]))
+                    verts.append(np.asarray(r, np.int32).reshape(-1, 2))
+                    n_verts += r.shape[0]
+                n_rings += len(payload)
+        self.n = len(rows)
+        self.n_rle = sum(1 for r in rows if r[6] == hip.MASK_RLE)
+        self.n_polygon = self.n - self.n_rle
+        self.n_counts, self.n_rings, self.n_vertices = n_counts, n_rings, n_verts
+        up = lambda v: (v + 7) // 8 * 8
+        self.rings_off = up(self.n * C.sizeof(hip.MaskSrc))
+        self.vertices_off = self.rings_off + 24 * max(n_rings, 1)
+        self.counts_off = self.vertices_off + 8 * max(n_verts, 1)
+        self.blob = np.zeros(up(self.counts_off + 4 * max(n_counts, 1)), np.uint8)
+        table = (hip.MaskSrc * self.n).from_buffer(self.blob)
+        for t, (dst_off, pay_off, pitch, h, w, pay_len, kind) in zip(table, rows):
+            t.dst_off, t.pay_off, t.pitch, t.h, t.w, t.pay_len, t.kind = dst_off, pay_off, pitch, h, w, pay_len, kind
+        del table                                                          # (a ctypes view pins the array's buffer)
+        if rings:
+            self.blob[self.rings_off:self.rings_off + 24 * n_rings] = np.asarray(rings, np.int64).reshape(-1).view(np.uint8)
+            self.blob[self.vertices_off:self.vertices_off + 8 * n_verts] = np.concatenate(verts).reshape(-1).view(np.uint8)
+        if counts:
+            self.blob[self.counts_off:self.counts_off + 4 * n_counts] = np.concatenate(counts).view(np.uint8)
+        self.host_addr = self.dev_addr = None
+        self._keep = None
+
+    def place(self, host_addr, dev_addr, keep=None):
+        """the block's bytes lie at `host_addr` (host) and, once the caller's copy has run, at `dev_addr` (device); both 8-byte aligned"""
+        if host_addr % 8 or (dev_addr or 0) % 8:
+            raise ValueError("MaskSources.place: both addresses must be 8-byte aligned")
+        self.host_addr, self.dev_addr, self._keep = int(host_addr), None if dev_addr is None else int(dev_addr), keep
+        return self
+
+    def upload(self, device):
+        """a pinned copy of the block and one asynchronous copy to `device` on the current stream"""
+        pinned = torch.from_numpy(self.blob).pin_memory()
+        dev = pinned.to(device, non_blocking=True)
+        return self.place(pinned.data_ptr(), dev.data_ptr(), keep=(pinned, dev))
+
+
+def desc_slots(descs, layout):
+    """(offset, pitch) of every descriptor of `descs` (an EvalStaging): layout "out" = the prediction slots (out_off, what
+    iou_batch / predict_batch write), "mask" = the ground-truth slots (mask_off)"""
+    if layout not in ("out", "mask"):
+        raise ValueError("desc_slots: layout must be 'out' or 'mask', got %r" % (layout,))
+    return [(descs.descs[i].out_off if layout == "out" else descs.descs[i].mask_off, descs.descs[i].pitch) for i in range(descs.n)]
+
+
+def decode_work(srcs, device, out=None):
+    """the scratch of `decode_masks_batch` for these sources (per mask the run ends of an RLE or the bit plane of a polygon): `out`
+    when it is large enough, a new int64 buffer otherwise.  Nothing has to be zeroed."""
+    if not isinstance(srcs, MaskSources):
+        raise ValueError("decode_work: srcs must be an evalpost.MaskSources, got %r" % (srcs,))
+    words = (hip.load().cris_mask_decode_work_bytes(srcs.blob.ctypes.data_as(C.c_void_p), srcs.n) + 7) // 8
+    if out is not None and out.numel() >= words:
+        return out
+    return torch.empty(words + words // 4, dtype=torch.int64, device=device)
+
+
+def decode_masks_batch(srcs, out, work=None):
+    """Decode every mask of `srcs` (a placed or uploaded MaskSources: RLE and polygon rows mixed) into the packed uint8 buffer `out`
+    on the device: mask i becomes h rows of pitch bytes at its dst_off - 0 / 255 at x < w, 0 at w <= x < pitch, byte for byte what
+    EvalStaging.pack writes for rle.decode / polygon.decode of it.  Nothing else of `out` is touched (not the gaps between slots, not
+    the tail) and the payload is only read.  RLE rows: two launches (cris_rle_decode); polygon rows: one memset of `work` and two
+    launches (cris_polygon_fill); none depends on the content, integers only - the same bytes on every run.  work: scratch from
+    `decode_work` to reuse.  On the current stream; nothing is synchronised or read.  Returns `out`."""
+    if not isinstance(srcs, MaskSources):
+        raise ValueError("decode_masks_batch: srcs must be an evalpost.MaskSources, got %r" % (srcs,))
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < srcs.out_bytes:
+        raise ValueError("decode_masks_batch: out must be a contiguous uint8 buffer that holds every slot (%d bytes)" % srcs.out_bytes)
+    if out.device.type != "cuda":
+        raise RuntimeError("evalpost runs on the GPU only (no CPU fallback)")
+    if srcs.dev_addr is None:
+        raise ValueError("decode_masks_batch: the sources are not on the device (MaskSources.upload, or an EvalStaging's upload)")
+    if work is not None and (work.dtype != torch.int64 or not work.is_contiguous() or work.device != out.device):
+        raise ValueError("decode_masks_batch: work must be a contiguous int64 buffer on the device of `out`")
+    work = decode_work(srcs, out.device, work)
+    host, dev = srcs.host_addr, srcs.dev_addr
+    if srcs.n_rle:
+        hip.call("cris_rle_decode", host, dev, srcs.n, dev + srcs.counts_off, max(srcs.n_counts, 1), ptr(work), 8 * work.numel(), ptr(out),
+                 out.numel(), _stream())
+    if srcs.n_polygon:
+        hip.call("cris_polygon_fill", host, dev, srcs.n, dev + srcs.vertices_off, max(srcs.n_vertices, 1), host + srcs.rings_off,
+                 dev + srcs.rings_off, max(srcs.n_rings, 1), 3, ptr(work), 8 * work.numel(), ptr(out), out.numel(), _stream())
+    return out
+
+
+def rle_decode_batch(rles, descs, out, layout="out", work=None):
+    """The inverse of `rle_encode_batch` / `rle_collect`: rles[i] (an RLE dict) is decoded into descriptor i's slot of `out` (layout
+    "out": out_off, "mask": mask_off; `descs`: an EvalStaging).  One small upload of the counts, then `decode_masks_batch`."""
+    return _decode_for_descs("rle_decode_batch", "rle", rles, descs, out, layout, work)
+
+
+def polygon_fill_batch(polys, descs, out, layout="out", work=None):
+    """The inverse of `polygon_count_batch` / `polygon_collect`: polys[i] (a traced or simplified polygon dict) is filled even-odd
+    into descriptor i's slot of `out`, as `rle_decode_batch` places an RLE."""
+    return _decode_for_descs("polygon_fill_batch", "polygon", polys, descs, out, layout, work)
+
+
+def _decode_for_descs(name, kind, masks, descs, out, layout, work):
+    forms = [mask_form(m, "%s: mask %d" % (name, i)) for i, m in enumerate(masks)]
+    if len(forms) != descs.n:
+        raise ValueError("%s: %d masks for %d descriptors" % (name, len(forms), descs.n))
+    for i, f in enumerate(forms):
+        d = descs.descs[i]
+        if f[0] != kind or (f[1], f[2]) != (d.h_out, d.w_out):
+            raise ValueError("%s: mask %d must be a %s of %d x %d, got %s %d x %d" % (name, i, kind, d.h_out, d.w_out, f[0], f[1], f[2]))
+    if not torch.is_tensor(out) or out.device.type != "cuda":
+        raise RuntimeError("evalpost runs on the GPU only (no CPU fallback)")
+    srcs = MaskSources(forms, desc_slots(descs, layout)).upload(out.device)
+    return decode_masks_batch(srcs, out, work=work)

@@ -26,6 +26,10 @@ device and `evalpost.boundary_iou_batch` adds (intersection, union) of the two b
 `validate` / `inference` take `smooth=evalpost.Smooth(...)`: every predicted mask is opened, closed and has its holes filled on the
 device (in that order, before `components`) and the final masks are counted; the ground truth is never smoothed; `smooth_info`
 holds the holes and pixels filled per sample.
+
+A record's `mask` may also be a COCO RLE or a polygon dict (evalpost.mask_form): such ground truth goes up encoded and is decoded
+on the device before the first kernel that reads it; records with PNG bytes take the path they always took.  `score_results` scores
+two sequences of masks in any of those forms without a model - the same integer tables, read once.
 """
 import math
 
@@ -166,6 +170,83 @@ def plan_inference(masks, inverses, sents_per_image, multiple=8):
     return index + [index[-1]] * (_pad_to(len(index), multiple) - len(index)), masks, descs
 
 
+class ScoreResult:
+    """What `score_results` returns: `iou` (mean of the per-sample IoUs), `prec` (Pr@50 ... Pr@90), `overall_iou`, `per_sample` [n]
+    and the integer `counts` [n, 2] they come from (`metrics` / `overall_iou` of that table); with `boundary` also `boundary_iou`,
+    `boundary_prec`, `boundary_per_sample`, `boundary_counts` (None otherwise)."""
+
+    def __init__(self, counts, boundary_counts=None):
+        self.counts = counts
+        self.iou, self.prec, self.per_sample = metrics(counts)
+        self.overall_iou = overall_iou(counts)
+        self.boundary_counts = boundary_counts
+        self.boundary_iou = self.boundary_prec = self.boundary_per_sample = None
+        if boundary_counts is not None:
+            self.boundary_iou, self.boundary_prec, self.boundary_per_sample = metrics(boundary_counts)
+
+
+_IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def score_results(predictions, ground_truth, device, boundary=None, batch=64):
+    """Score masks against masks without a model -> ScoreResult: IoU, Pr@50 ... Pr@90 and overall IoU of predictions[i] against
+    ground_truth[i], the figures `Evaluator` reports, from a results file or any other source of masks.
+    predictions, ground_truth: two equally long sequences; every entry in any form `evalpost.mask_form` takes - a uint8 [h, w]
+    array, PNG bytes, an RLE dict (counts as str, bytes or list: the "segmentation" of a results JSON written from
+    predict(..., masks="rle") goes in as it is), a traced or simplified polygon dict, or a predict.Prediction holding one of them.
+    COCO's flat [x0, y0, ...] polygon lists are NOT accepted: polygon.to_coco drops holes and the "epsilon" marker and COCO fills such
+    lists as a union, not even-odd - exchange RLE.
+    Per batch of `batch` pairs both sides are decoded on the device into the two packed layouts (evalpost.decode_masks_batch:
+    predictions at out_off, ground truth at mask_off; arrays are packed on the host and uploaded), `evalpost.mask_iou_batch` adds
+    (intersection, union) to an integer table and, with boundary (True or an evalpost.Boundary), `boundary_iou_batch` the Boundary
+    IoU counts to a second one; the tables are read once, at the end.  A malformed entry or a pair of different sizes raises
+    ValueError naming its index before any device work for its batch."""
+    bspec = evalpost.boundary_spec(boundary, "score_results: boundary")
+    preds, gts = list(predictions), list(ground_truth)
+    if len(preds) != len(gts) or not preds:
+        raise ValueError("score_results: need two equally long, non-empty sequences, got %d predictions and %d ground-truth masks" % (len(preds), len(gts)))
+    if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= batch <= 65535:
+        raise ValueError("score_results: batch must be an integer in 1 .. 65535, got %r" % (batch,))
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("evalpost runs on the GPU only (no CPU fallback)")
+    total = len(preds)
+    tables = torch.zeros(2 if bspec is not None else 1, total, 2, dtype=torch.int32, device=device)
+    ring = [evalpost.EvalStaging(device) for _ in range(2)]
+    out = work = bwork = None
+    for lo in range(0, total, batch):
+        pf = [evalpost.mask_form(m, "score_results: prediction %d" % (lo + i)) for i, m in enumerate(preds[lo:lo + batch])]
+        gf = [evalpost.mask_form(m, "score_results: ground truth %d" % (lo + i)) for i, m in enumerate(gts[lo:lo + batch])]
+        for i, (p, g) in enumerate(zip(pf, gf)):
+            if (p[1], p[2]) != (g[1], g[2]) or p[1] < 1 or p[2] < 1:
+                raise ValueError("score_results: pair %d: the prediction is %d x %d, the ground truth %d x %d (both must be one positive size)"
+                                 % (lo + i, p[1], p[2], g[1], g[2]))
+        st = ring[(lo // batch) % 2].pack_encoded(gf, [(_IDENTITY, i, 0, i) for i in range(len(gf))]).upload()
+        work = st.decode(work)
+        slots = evalpost.desc_slots(st, "out")
+        arrays = [i for i, p in enumerate(pf) if p[0] == "array"]
+        if arrays:                                                 # packed on the host in the out_off layout, one copy
+            buf = torch.zeros(st.out_bytes, dtype=torch.uint8).pin_memory()
+            view = buf.numpy()
+            for i in arrays:
+                (off, pitch), (_, h, w, m) = slots[i], pf[i]
+                view[off:off + pitch * h].reshape(h, pitch)[:, :w] = m.numpy() if torch.is_tensor(m) else m
+            out = buf.to(device, non_blocking=True)
+        elif out is None or out.numel() < st.out_bytes:
+            out = torch.empty(st.out_bytes + st.out_bytes // 4, dtype=torch.uint8, device=device)
+        enc = [i for i, p in enumerate(pf) if p[0] != "array"]
+        if enc:
+            srcs = evalpost.MaskSources([pf[i] for i in enc], [slots[i] for i in enc]).upload(device)
+            work = evalpost.decode_work(srcs, device, work)
+            evalpost.decode_masks_batch(srcs, out, work=work)
+        evalpost.mask_iou_batch(out, st, st.masks, tables[0], lo)
+        if bspec is not None:
+            bwork = evalpost.boundary_work(st, device, bwork)
+            evalpost.boundary_iou_batch(out, st, st.masks, evalpost.boundary_radii(st, bspec), tables[1], lo, work=bwork)
+    read = tables.cpu().numpy()                                    # the call's one read
+    return ScoreResult(read[0], read[1] if bspec is not None else None)
+
+
 class Evaluator:
     """`Evaluator(model, pipeline, thr=0.35)`: model - any callable `(img, word) -> logits [B, 1, h, w]` (an InferenceRunner, the
     drop-in CRIS module in eval mode); when it also offers `segment(img, word, image_index)` or `segment_expressions`, `inference`
@@ -199,6 +280,27 @@ class Evaluator:
             if tuple(m.shape) != tuple(int(v) for v in p["ori_size"]):
                 raise ValueError("record %s: mask is %s, image %s" % (p["mask_dir"], tuple(m.shape), tuple(p["ori_size"])))
         return masks
+
+    def _ground_truth(self, recs, params):
+        """-> (masks, encoded).  Records whose `mask` is PNG bytes, all of them: (`_masks`, False) - the host decode and the path of
+        every pass so far.  Otherwise (`evalpost.mask_form` of every record's mask, True): RLE and polygon ground truth stays encoded
+        for the device, a PNG among them is decoded on the host; the size check against `ori_size` is the same."""
+        if all(isinstance(r["mask"], (bytes, bytearray, memoryview)) for r in recs):
+            return self._masks(recs, params), False
+        forms = [evalpost.mask_form(r["mask"], "record %s" % p["mask_dir"]) for r, p in zip(recs, params)]
+        for f, p in zip(forms, params):
+            if (f[1], f[2]) != tuple(int(v) for v in p["ori_size"]):
+                raise ValueError("record %s: mask is %s, image %s" % (p["mask_dir"], (f[1], f[2]), tuple(int(v) for v in p["ori_size"])))
+        return forms, True
+
+    def _upload(self, masks, descs, encoded):
+        """the batch's staging, packed and uploaded; encoded ground truth is decoded into its slots on the current stream, before
+        any kernel that reads `st.masks` is issued"""
+        if not encoded:
+            return self._staging().pack(masks, descs).upload()
+        st = self._staging().pack_encoded(masks, descs).upload()
+        self._dec_work = st.decode(getattr(self, "_dec_work", None))
+        return st
 
     def _clean_counts(self, spec, probs, st, table, row0, info, out=None, sspec=None, sinfo=None):
         """one batch with a Components and / or a Smooth spec: iou_batch writes the masks (its own counts go to a scratch table), the
@@ -290,7 +392,8 @@ class Evaluator:
             if n < batch_size:                                     # short last batch: repeat its last sample, one graph shape
                 rep = torch.tensor(list(range(n)) + [n - 1] * (batch_size - n), device=self.device)
                 img, word = img[rep], word[rep]
-            st = self._staging().pack(*plan_validate(self._masks(recs, params), [p["inverse"] for p in params])).upload()
+            masks, encoded = self._ground_truth(recs, params)
+            st = self._upload(*plan_validate(masks, [p["inverse"] for p in params]), encoded)
             probs = evalpost.sigmoid_upsample(self.model(img, word), img.shape[-2], img.shape[-1])
             if spec is None and sspec is None:
                 out = None if bspec is None else self._boundary_masks(st)
@@ -333,12 +436,13 @@ class Evaluator:
                 rep = torch.tensor(list(range(n)) + [n - 1] * (images_per_batch - n), device=self.device)
                 img = img[rep]
             sents = [s for p in params for s in p["sents"]]
-            index, masks, descs = plan_inference(self._masks(recs, params), [p["inverse"] for p in params],
+            masks, encoded = self._ground_truth(recs, params)
+            index, masks, descs = plan_inference(masks, [p["inverse"] for p in params],
                                                  [len(p["sents"]) for p in params])
             K = len(sents)
             word = self.pipe.tok.tokenize(sents + [sents[-1]] * (len(index) - K), self.pipe.word_length, True)
             word = word.to(self.device, non_blocking=True)
-            st = self._staging().pack(masks, descs).upload()
+            st = self._upload(masks, descs, encoded)
             if self._segment is not None:
                 logits = self._segment(img, word, index)
             else:
@@ -392,7 +496,8 @@ class Evaluator:
                 if n < batch_size:                                 # short last batch: repeat its last sample, one graph shape
                     rep = torch.tensor(list(range(n)) + [n - 1] * (batch_size - n), device=self.device)
                     img, word = img[rep], word[rep]
-                st = self._staging().pack(*plan_validate(self._masks(recs, params), [p["inverse"] for p in params])).upload()
+                masks, encoded = self._ground_truth(recs, params)
+                st = self._upload(*plan_validate(masks, [p["inverse"] for p in params]), encoded)
                 probs = evalpost.sigmoid_upsample(self.model(img, word), img.shape[-2], img.shape[-1])
                 evalpost.iou_sweep_batch(probs, st, st.masks, table, lo, thr)
         else:
@@ -407,12 +512,13 @@ class Evaluator:
                     rep = torch.tensor(list(range(n)) + [n - 1] * (images_per_batch - n), device=self.device)
                     img = img[rep]
                 sents = [s for p in params for s in p["sents"]]
-                index, masks, descs = plan_inference(self._masks(recs, params), [p["inverse"] for p in params],
+                masks, encoded = self._ground_truth(recs, params)
+                index, masks, descs = plan_inference(masks, [p["inverse"] for p in params],
                                                      [len(p["sents"]) for p in params])
                 K = len(sents)
                 word = self.pipe.tok.tokenize(sents + [sents[-1]] * (len(index) - K), self.pipe.word_length, True)
                 word = word.to(self.device, non_blocking=True)
-                st = self._staging().pack(masks, descs).upload()
+                st = self._upload(masks, descs, encoded)
                 if self._segment is not None:
                     logits = self._segment(img, word, index)
                 else:

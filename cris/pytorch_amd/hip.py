@@ -217,6 +217,13 @@ class EvalDesc(C.Structure):
                 ("mask_off", L), ("out_off", L), ("pitch", I), ("pad_", I)]
 
 
+MASK_RLE, MASK_POLYGON = 0, 1     # CRIS_MASK_* of include/cris_hip.h
+
+
+class MaskSrc(C.Structure):
+    _fields_ = [("dst_off", L), ("pay_off", L), ("pitch", I), ("h", I), ("w", I), ("pay_len", I), ("kind", I), ("pad_", I)]
+
+
 class JpegInfo(C.Structure):
     _fields_ = [("width", I), ("height", I), ("ncomp", I), ("hmax", I), ("vmax", I), ("mcus_x", I), ("mcus_y", I),
                 ("restart_interval", I),
@@ -254,7 +261,7 @@ STRUCTS = {
     "cris_conv_gemm_fp8_params": ConvGemmFp8Params, "cris_pack_fp8_desc": PackFp8Desc,
     "cris_bn_apply_params": BnApplyParams, "cris_bn_bwd_params": BnBwdParams, "cris_ln_fwd_params": LnFwdParams,
     "cris_ln_bwd_params": LnBwdParams, "cris_sum_entry": SumEntry, "cris_sum_group": SumGroup, "cris_attn_params": AttnParams, "cris_adam_desc": AdamDesc, "cris_ema_desc": EmaDesc, "cris_p2p_params": P2PParams, "cris_p2p_link": P2PLink, "cris_p2p_arena_params": P2PArenaParams, "cris_zero_ranges": ZeroRanges,
-    "cris_sample_desc": SampleDesc, "cris_eval_desc": EvalDesc, "cris_jpeg_info": JpegInfo, "cris_jpeg_image": JpegImage,
+    "cris_sample_desc": SampleDesc, "cris_eval_desc": EvalDesc, "cris_mask_src": MaskSrc, "cris_jpeg_info": JpegInfo, "cris_jpeg_image": JpegImage,
 }
 
 # name -> (restype, argtypes); struct launchers take (struct*, stream)
@@ -377,6 +384,9 @@ _SIGS = {
     "cris_morph_masks": (I, [P, C.c_size_t, P, P, I, P, I, P, P, P, C.c_size_t, P, C.c_size_t, P]),
     "cris_fill_holes_work_bytes": (C.c_size_t, [C.c_size_t]),
     "cris_fill_holes": (I, [P, C.c_size_t, P, P, I, I, I, P, C.c_size_t, P, C.c_size_t, P, I, P]),
+    "cris_mask_decode_work_bytes": (C.c_size_t, [P, I]),
+    "cris_rle_decode": (I, [P, P, I, P, C.c_size_t, P, C.c_size_t, P, C.c_size_t, P]),
+    "cris_polygon_fill": (I, [P, P, I, P, C.c_size_t, P, P, C.c_size_t, I, P, C.c_size_t, P, C.c_size_t, P]),
     "cris_preprocess_batch": (I, [P, I, I, I, P, P, P, P, P, P, P, P]),
     "cris_gray_sum_batch": (I, [P, P, I, P, P]),
     "cris_preprocess_batch_aug": (I, [P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),

@@ -89,6 +89,19 @@ class LmdbRecords:
         self.__init__(st["path"])
 
 
+def mask_array(rec):
+    """The ground-truth mask of a record on the host, whatever form `rec["mask"]` has -> uint8 [h, w] (a CPU tensor for PNG bytes,
+    exactly what pngdec.decode_gray returns; a numpy array of 0 / 255 otherwise): the bytes of an 8-bit gray PNG
+    (tools/folder2lmdb.py), a COCO RLE {"size", "counts"} with counts as str, bytes or a list (what the reference's
+    tools/refer.py:getMask holds before it ever makes a PNG), or a traced / simplified polygon dict (polygon.py).  Validated by
+    rle.py / polygon.py before anything is decoded (evalpost.mask_form)."""
+    mask = rec["mask"]
+    if isinstance(mask, (bytes, bytearray, memoryview)):
+        return pngdec.decode_gray(mask)
+    from . import evalpost
+    return evalpost.mask_to_array(evalpost.mask_form(mask, "record %s: mask" % (rec.get("seg_id", "?"),)))
+
+
 _LEFT_RIGHT = re.compile(r"\b(left|right)", re.IGNORECASE)
 
 
@@ -125,7 +138,7 @@ class RecordPipeline:
         if self.augment is not None:
             params = inputpipe.augment_params(self.augment, rng.random((len(records), 8)), self.pre.input_size)
         images = jpegdec.decode_batch([r["img"] for r in records], self.device, threads=self.threads)
-        masks = [pngdec.decode_gray(r["mask"]) for r in records] if self.mode == "train" else None
+        masks = [mask_array(r) for r in records] if self.mode == "train" else None
         if params is None:
             img, mask, _, invs = self.pre(images, masks)
         else:

@@ -26,7 +26,7 @@ typedef uint16_t cris_bf16;
 const char* cris_last_error(void);
 /* CRIS_ABI_VERSION moves whenever an exported signature or struct changes or a symbol is added; a binding compares cris_abi_version() with the
  * value it was written against and refuses a library of another version (a stale build loaded with new argument lists would
- * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_rle_encode / cris_rle_work_bytes (COCO run-length encoding of the packed masks on the device) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/rle.hip), every other launcher keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_erode_masks / cris_boundary_iou_batch / cris_boundary_work_bytes (square-structuring-element erosion of the packed masks and the Boundary IoU counts built on it) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/morph.hip), the radii travel as a separate int32 array, every other launcher keeps its signature, its kernel and its results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_morph_masks / cris_fill_holes / cris_fill_holes_work_bytes (mask smoothing: chained dilation / erosion of the packed masks, hence opening and closing, and hole filling) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc, the operation codes and radii travel as separate int32 arrays, cris_erode_masks / cris_boundary_iou_batch / cris_label_components / cris_filter_components keep their signatures, their launches and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_polygon_count / cris_polygon_trace / cris_polygon_work_bytes / cris_polygon_trace_work_bytes (polygon tracing of the packed masks on the device) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/polygon.hip), cris_rle_encode and every other launcher keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_polygon_simplify / cris_polygon_simplify_work_bytes (Douglas-Peucker simplification of the traced rings on the device) were added at 8 without moving it in the same way: two new symbols in a translation unit of their own (csrc/simplify.hip) that read what cris_polygon_trace left, cris_polygon_count / cris_polygon_trace keep their signatures, their launches and their results, and a binding that knows the two binds them at load, so a library without them is refused there */
+ * mis-read them silently, and one without a new symbol fails only at the first call).  2: cris_step_advance took its fourth argument (round 5); 3, 4: round 6 (arena exchange; row strides of the weight packs); 5: the FP8 inference kernels; 6: cris_eval_iou_batch; 7: cris_grad_sumsq / cris_grad_clip_finalize; 8: cris_grad_accumulate / cris_step_advance_micro; the EMA symbols (cris_ema_advance / cris_ema_update / cris_ema_blocks, cris_ema_desc) were added at 8 WITHOUT moving it: no existing signature or struct changed, and a binding written for them binds every symbol and checks every struct size at load, so a library without them is still refused there; cris_adam_schedule_lrs (the per-step learning-rate schedule) was likewise added at 8 without moving it: it is a new symbol over the unchanged cris_adam_desc, no existing signature or struct changed, and a binding that knows it binds it at load, so a library without it is refused there too; cris_adamw_step (one weight decay per tensor, coupled or decoupled) was added at 8 without moving it in the same way: a new symbol over the unchanged cris_adam_desc, cris_adam_step[_amp] keep their signatures and their results, and a binding that knows it binds it at load; cris_seg_loss_fwd / cris_seg_loss_bwd / cris_seg_loss_ws_floats (the configurable segmentation loss: weighted BCE plus soft Dice) were added at 8 without moving it in the same way: three new symbols that take plain pointers and scalars, no struct and no existing signature changed, cris_bce_fwd / cris_bce_bwd keep their code and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_gray_sum_batch / cris_preprocess_batch_aug (training-time augmentation of the input pipeline) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_sample_desc, cris_preprocess_batch keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_predict_masks_batch (masks, areas, boxes and scores for unlabeled images in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_eval_desc_fill keep their signatures and their results, and a binding that knows it binds it at load, so a library without it is refused there (the tests of the earlier additions pin the number 8, which is why a new symbol alone does not move it); cris_eval_iou_sweep_batch (the intersection / union counts of a batch at up to 64 thresholds in one launch) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_eval_desc, cris_eval_iou_batch and cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_attn_plan (which kernel an attention launcher takes: host arithmetic for the per-element attention tests) was added at 8 without moving it in the same way: one new symbol over the unchanged cris_attn_params, cris_attn_fwd / cris_attn_bwd_dq / cris_attn_bwd_dkv keep their signatures, their kernels and their results, and a binding that knows it binds it at load, so a library without it is refused there; cris_label_components / cris_filter_components / cris_filter_components_work_bytes / cris_mask_iou_batch (connected-component clean-up of the predicted masks: keep the largest component, drop the small ones) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc, cris_eval_iou_batch / cris_eval_iou_sweep_batch / cris_predict_masks_batch keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_rle_encode / cris_rle_work_bytes (COCO run-length encoding of the packed masks on the device) were added at 8 without moving it in the same way: two new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/rle.hip), every other launcher keeps its signature, its kernel and its results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_erode_masks / cris_boundary_iou_batch / cris_boundary_work_bytes (square-structuring-element erosion of the packed masks and the Boundary IoU counts built on it) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/morph.hip), the radii travel as a separate int32 array, every other launcher keeps its signature, its kernel and its results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_morph_masks / cris_fill_holes / cris_fill_holes_work_bytes (mask smoothing: chained dilation / erosion of the packed masks, hence opening and closing, and hole filling) were added at 8 without moving it in the same way: three new symbols over the unchanged cris_eval_desc, the operation codes and radii travel as separate int32 arrays, cris_erode_masks / cris_boundary_iou_batch / cris_label_components / cris_filter_components keep their signatures, their launches and their results, and a binding that knows the three binds them at load, so a library without them is refused there; cris_polygon_count / cris_polygon_trace / cris_polygon_work_bytes / cris_polygon_trace_work_bytes (polygon tracing of the packed masks on the device) were added at 8 without moving it in the same way: four new symbols over the unchanged cris_eval_desc in a translation unit of their own (csrc/polygon.hip), cris_rle_encode and every other launcher keep their signatures, their kernels and their results, and a binding that knows the four binds them at load, so a library without them is refused there; cris_polygon_simplify / cris_polygon_simplify_work_bytes (Douglas-Peucker simplification of the traced rings on the device) were added at 8 without moving it in the same way: two new symbols in a translation unit of their own (csrc/simplify.hip) that read what cris_polygon_trace left, cris_polygon_count / cris_polygon_trace keep their signatures, their launches and their results, and a binding that knows the two binds them at load, so a library without them is refused there; cris_rle_decode / cris_polygon_fill / cris_mask_decode_work_bytes (encoded masks decoded into the packed layouts on the device) were added at 8 without moving it in the same way: three new symbols and one new struct, cris_mask_src, in a translation unit of their own (csrc/decode.hip), cris_eval_desc and every other launcher keep their layouts, their launches and their results, and a binding that knows the three binds them and checks the struct's size at load, so a library without them is refused there */
 #define CRIS_ABI_VERSION 8
 int cris_abi_version(void);
 /* sizeof() of the parameter structs, so the Python mirror (ctypes) can be checked without a GPU */
@@ -716,6 +716,47 @@ size_t cris_fill_holes_work_bytes(size_t mask_bytes);
 int cris_fill_holes(unsigned char* masks, size_t mask_bytes, const cris_eval_desc* descs_host, const cris_eval_desc* descs_dev, int n,
                     int connectivity, int max_area, int* labels, size_t label_words, void* work, size_t work_bytes, long long* info,
                     int info_rows, void* stream);
+/* Encoded masks decoded into the packed layouts above (csrc/decode.hip, csrc/decode_core.h; DESIGN.md 9b): the inverse of cris_rle_encode
+ * and of cris_polygon_count / cris_polygon_trace / cris_polygon_simplify; rle.decode and polygon.decode (host) are the definitions.  A
+ * cris_mask_src row names ONE mask: its slot - h rows of pitch bytes at dst_off of `out`, so that a ground-truth slot (a descriptor's
+ * mask_off) and a prediction slot (out_off) are filled alike, and several descriptors may name a mask that is decoded once - its
+ * payload and its kind.  Both entry points take the whole table and serve the rows of their kind only; for each such row they write
+ * 0 / 255 at x < w and 0 at w <= x < pitch of every row and nothing else (not the gap to the next slot, not the tail, no slot of the
+ * other kind).  The payload is only read.
+ *   CRIS_MASK_RLE      pay_off / pay_len: the first word and the number of the mask's counts in `counts` (uint32, COCO order:
+ *     column-major, i = x * h + y, the first run background).  Pixel i is foreground iff the number of run ends <= i is odd; runs of
+ *     length zero are legal anywhere.  Counts that do not sum to h * w (the host validates them first) change values, never addresses.
+ *     Two launches: scan of the counts per mask, one upper-bound search per pixel with a dword stored per 4 pixels.
+ *   CRIS_MASK_POLYGON  pay_off / pay_len: the first row and the number of the mask's rows in the ring table, rows of ring_stride
+ *     (3 .. 8) 64-bit words that start (index of the mask in this table, offset in pairs, length) - the first columns of what the
+ *     tracer and the simplifier leave; the rows of one mask are adjacent and their vertices follow each other in `vertices` (int32
+ *     (x, y) pairs, pixel corners).  Even-odd filling sampled at pixel centres in exact integers: every non-horizontal edge
+ *     (x0, y0) -> (x1, y1) oriented downwards toggles, on each centre line py = y0 .. y1 - 1, the pixels at x >= px,
+ *     px = x0 - floor((dy - num) / (2 dy)), num = (2 py + 1 - 2 y0) dx, clipped to [0, w] (w toggles nothing); rows outside [0, h) are
+ *     skipped.  One memset of the work buffer and two launches: one 64-bit integer atomic XOR per (edge, row) into the mask's bit plane,
+ *     then the inclusive prefix parity of every row, a dword stored per 4 pixels.
+ * work: device scratch of cris_mask_decode_work_bytes(srcs_host, n) bytes - n slots of the maximum over the table of ceil(pay_len / 2)
+ * (RLE: the run ends) and h * ceil(w / 64) (polygon: the plane) 64-bit words; 0 for a NULL table or n outside 1 .. 65535; nothing has to
+ * be zeroed, and both entry points may use one buffer on one stream.  Integers only, the XORs commute: the same bytes on every run.
+ * Checked on the host before the first launch: operands non-NULL, n in 1 .. 65535, alignment (work, the tables, vertices 8-byte; counts,
+ * out and every dst_off 4-byte), work_bytes, and per row of EITHER kind its kind, h, w >= 1, h * w < 2^31 ((h + 1) * (w + 1) <= 2^28 for
+ * a polygon), w <= pitch, pitch a multiple of 4, pitch * h < 2^31, the slot inside out_bytes, the payload inside count_words / ring_rows,
+ * and per ring row the mask it names, length >= 1, its vertices inside vertex_pairs and adjacent to the previous ring's. */
+#define CRIS_MASK_RLE 0
+#define CRIS_MASK_POLYGON 1
+typedef struct {
+    long dst_off;
+    long pay_off;
+    int pitch, h, w;
+    int pay_len;
+    int kind, pad_;
+} cris_mask_src;
+size_t cris_mask_decode_work_bytes(const cris_mask_src* srcs_host, int n);
+int cris_rle_decode(const cris_mask_src* srcs_host, const cris_mask_src* srcs_dev, int n, const unsigned* counts, size_t count_words,
+                    void* work, size_t work_bytes, unsigned char* out, size_t out_bytes, void* stream);
+int cris_polygon_fill(const cris_mask_src* srcs_host, const cris_mask_src* srcs_dev, int n, const int* vertices, size_t vertex_pairs,
+                      const long long* rings_host, const long long* rings_dev, size_t ring_rows, int ring_stride, void* work,
+                      size_t work_bytes, unsigned char* out, size_t out_bytes, void* stream);
 /* ---- input preprocessing (reference utils/dataset.py:146-168 RefDataset.__getitem__, :207-221 convert; csrc/inputpipe.hip) ----
  * One launch per batch: img_out[b] = ((cv2.warpAffine(rgb_u8, mat, (S_w, S_h), INTER_CUBIC, borderValue=border_rgb).float()
  * / 255 - mean) / std) as [3][S_h][S_w] (through lut_img [3][256]), mask_out[b] = cv2.warpAffine(mask_u8, mat, ...,

@@ -14,7 +14,13 @@ whole `Evaluator.sweep` pass against a whole `validate` pass) and writes profile
 
 `--boundary` measures Boundary IoU instead (boundary_main: the three launches of `boundary_iou_batch` next to the `iou_batch`
 launch that writes the masks, the host route they replace - scipy.ndimage.binary_erosion per mask - and a whole `validate` pass
-with and without the spec) and writes profiles/boundary_iou.md."""
+with and without the spec) and writes profiles/boundary_iou.md.
+
+`--decode` measures the mask decoders instead (decode_main: device time of `cris_rle_decode` and `cris_polygon_fill` on 24 masks of
+480 x 640, `evaluate.score_results` on them against the host route it replaces, a whole `validate` pass with RLE ground truth
+against the same pass with PNG ground truth, the bytes each uploads per batch) and prints the table; `--png-pass` prints the rounds
+of the PNG pass alone, and `--tree DIR` imports the package from another checkout, so that fresh processes can alternate between a
+build of the parent commit and this one (profiles/mask_decode.md)."""
 import argparse
 import io
 import os
@@ -27,7 +33,7 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.abspath(sys.argv[sys.argv.index("--tree") + 1]) if "--tree" in sys.argv[:-1] else ROOT)
 from cris.pytorch_amd import arch, evalpost, evaluate, pngdec, records, tokenizer      # noqa: E402
 from cris.pytorch_amd.infer import InferenceRunner      # noqa: E402
 
@@ -311,6 +317,157 @@ def boundary_main(a, dev, recs, pipe, runner):
         f.write(text)
 
 
+def png_pass(a, recs, pipe, runner):
+    """--png-pass: the rounds of a whole `Evaluator.validate` pass over PNG records, samples/s, one line (uses nothing the parent
+    commit lacks: run it with --tree on either checkout)"""
+    ev = evaluate.Evaluator(runner, pipe)
+    ev.validate(recs[:2 * BATCH], batch_size=BATCH)                # warm-up: eager call, graph capture
+    rounds = []
+    for _ in range(ROUNDS):
+        t0 = time.perf_counter()
+        ev.validate(recs, batch_size=BATCH)
+        torch.cuda.synchronize()
+        rounds.append(len(recs) / (time.perf_counter() - t0))
+    print("png-pass %s | %s | median %.1f samples/s" % (os.path.dirname(os.path.dirname(os.path.abspath(evaluate.__file__))),
+                                                         " ".join("%.1f" % v for v in rounds), statistics.median(rounds)))
+
+
+def decode_masks(n=24, h=480, w=640, seed=0):
+    """n masks of h x w as predictions look: a blob with a hole, a bar and specks; and the same shifted, as ground truth"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    out = []
+    for i in range(n):
+        cx, cy, rx, ry = rng.uniform(0.3, 0.7) * w, rng.uniform(0.3, 0.7) * h, rng.uniform(0.1, 0.3) * w, rng.uniform(0.1, 0.3) * h
+        m = ((xx - cx) / rx) ** 2 + ((yy - cy) / ry) ** 2 < 1.0
+        m &= ~(((xx - cx - 20) / (rx / 4)) ** 2 + ((yy - cy + 10) / (ry / 4)) ** 2 < 1.0)
+        m |= (np.abs(xx - 60 - 5 * i) < 9) & (yy > h - 80)
+        m |= rng.random((h, w)) < 0.0005
+        out.append(m.astype(np.uint8) * 255)
+    return out, [np.roll(m, (7, 5), (0, 1)) for m in out]
+
+
+def decode_main(a, dev, recs, pipe, runner):
+    """--decode: (a)-(c) device time of the decoders on 24 masks of 480 x 640 (events around `decode_masks_batch`, sources
+    resident); (d) `score_results` on those masks as RLE against (e) the host route it replaces - `rle.decode` per mask, pack,
+    upload, `mask_iou_batch`, one read; (f) / (g) a whole `Evaluator.validate` pass with PNG and with RLE ground truth,
+    interleaved, and the bytes each uploads per batch."""
+    from cris.pytorch_amd import polygon, rle
+    preds, gts = decode_masks()
+    n = len(preds)
+    ident = np.array([[1.0, 0, 0], [0, 1.0, 0]])
+    st = evalpost.EvalStaging(dev).pack_sizes([m.shape for m in preds], [(ident, i, 0, i) for i in range(n)]).upload()
+    slots = evalpost.desc_slots(st, "out")
+    as_rle = [rle.encode(m) for m in preds]
+    as_poly = [polygon.encode(m) for m in preds]
+    as_simple = [polygon.simplify(p, 1.0) for p in as_poly]
+    out = torch.empty(st.out_bytes, dtype=torch.uint8, device=dev)
+    t_dev, equal, sizes = [], [], []
+    calls = 40 * a.reps
+    for items, want in ((as_rle, preds), (as_poly, preds), (as_simple, [polygon.decode(p) for p in as_simple])):
+        srcs = evalpost.MaskSources([evalpost.mask_form(x) for x in items], slots).upload(dev)
+        work = evalpost.decode_work(srcs, dev)
+        out.fill_(0x7F)
+        evalpost.decode_masks_batch(srcs, out, work=work)
+        got = out.cpu().numpy()
+        equal.append(all(np.array_equal(got[o:o + p * m.shape[0]].reshape(m.shape[0], p)[:, :m.shape[1]], m) for (o, p), m in zip(slots, want)))
+        sizes.append(srcs.blob.size)
+        rounds = []
+        for _ in range(ROUNDS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(calls):
+                evalpost.decode_masks_batch(srcs, out, work=work)
+            e1.record()
+            torch.cuda.synchronize()
+            rounds.append(e0.elapsed_time(e1) / calls)
+        t_dev.append(rounds)
+
+    gt_rle = [rle.encode(m) for m in gts]
+    json_rle = [rle.to_json(r) for r in as_rle]                    # str counts, as a results file holds them
+
+    def scorer():
+        return evaluate.score_results(json_rle, gt_rle, dev).counts
+
+    host_st = evalpost.EvalStaging(dev)
+
+    def host_route():
+        p_arr, g_arr = [rle.decode(r) for r in json_rle], [rle.decode(r) for r in gt_rle]
+        hs = host_st.pack(g_arr, [(ident, i, 0, i) for i in range(n)]).upload()
+        buf = torch.zeros(hs.out_bytes, dtype=torch.uint8).pin_memory()
+        view = buf.numpy()
+        for i, m in enumerate(p_arr):
+            d = hs.descs[i]
+            view[d.out_off:d.out_off + d.pitch * d.h_out].reshape(d.h_out, d.pitch)[:, :d.w_out] = m
+        table = torch.zeros(n, 2, dtype=torch.int32, device=dev)
+        evalpost.mask_iou_batch(buf.to(dev, non_blocking=True), hs, hs.masks, table, 0)
+        return table.cpu().numpy()
+
+    same_counts = bool(np.array_equal(scorer(), host_route()))
+    t_score, t_host = [], []
+    for _ in range(ROUNDS):
+        t_score.append(timed(scorer, a.reps) * 1e3)
+        t_host.append(timed(host_route, a.reps) * 1e3)
+
+    recs_rle = [dict(r, mask=rle.encode(pngdec.decode_gray(r["mask"]).numpy())) for r in recs]
+    uploads = []
+    real = evalpost.EvalStaging.upload
+    evalpost.EvalStaging.upload = lambda self: (real(self), uploads.append(self.last_upload_bytes))[0]
+    ev = evaluate.Evaluator(runner, pipe)
+    ev.validate(recs[:2 * BATCH], batch_size=BATCH)                # warm-up: eager call, graph capture
+    ev.validate(recs_rle[:2 * BATCH], batch_size=BATCH)
+    p_png, p_rle, b_png, b_rle, last = [], [], [], [], []
+    for _ in range(ROUNDS):
+        for rs, rate, nbytes in ((recs, p_png, b_png), (recs_rle, p_rle, b_rle)):
+            del uploads[:]
+            t0 = time.perf_counter()
+            ev.validate(rs, batch_size=BATCH)
+            torch.cuda.synchronize()
+            rate.append(len(rs) / (time.perf_counter() - t0))
+            nbytes += uploads
+            last.append(ev.counts.copy())
+    same_pass = bool(np.array_equal(last[-2], last[-1]))
+    evalpost.EvalStaging.upload = real
+
+    def row(name, v, unit):
+        return "| %s | %s | %.3f | %.3f | %.3f %s |" % (name, " ".join("%.3f" % x for x in v), min(v), max(v), statistics.median(v), unit)
+
+    med = statistics.median
+    lines = ["`python tools/eval_bench.py --decode --records %d --reps %d` on %s: %d masks of 480 x 640 (a blob with a hole, a bar,"
+             % (a.records, a.reps, torch.cuda.get_device_name(0), n),
+             "specks; the ground truth is the mask shifted by (7, 5)); R50, %dx%d, synthetic weights, %d synthetic records, batch %d;"
+             % (SIZE, SIZE, a.records, BATCH),
+             "%d rounds with the arms interleaved.  (a)-(c): events around %d back-to-back `decode_masks_batch` calls, sources resident."
+             % (ROUNDS, calls),
+             "(d), (e): host clocks around %d calls that end with the counts on the host.  (f), (g): whole passes (JPEG decode, letter-box,"
+             % a.reps,
+             "forward, post-processing, one host read).", "",
+             "| arm | rounds | min | max | median |", "|---|---|---|---|---|",
+             row("(a) `cris_rle_decode`, %d masks, device ms" % n, t_dev[0], "ms"),
+             row("(b) `cris_polygon_fill`, traced polygons, device ms", t_dev[1], "ms"),
+             row("(c) `cris_polygon_fill`, simplified at 1.0, device ms", t_dev[2], "ms"),
+             row("(d) `score_results` on %d RLE pairs, ms" % n, t_score, "ms"),
+             row("(e) host route: `rle.decode` x %d, pack, upload, `mask_iou_batch`, ms" % (2 * n), t_host, "ms"),
+             row("(f) whole `Evaluator.validate` pass, PNG ground truth, samples/s", p_png, "samples/s"),
+             row("(g) whole `Evaluator.validate` pass, RLE ground truth, samples/s", p_rle, "samples/s"), "",
+             "* Every decoded slot equals the host decode: RLE %s, traced polygons %s, simplified polygons %s." % tuple(equal),
+             "* Tables and payload of the %d masks: %d bytes as RLE, %d as traced polygons, %d simplified; the masks themselves %d bytes."
+             % (n, sizes[0], sizes[1], sizes[2], n * 480 * 640),
+             "* (d) and (e) give equal counts: %s.  (e) / (d) = %.2f; spread of (e) over its rounds %.3f ms."
+             % (same_counts, med(t_host) / med(t_score), max(t_host) - min(t_host)),
+             "* (g) / (f) = %.3f in samples/s (per round %s); the two passes give equal counts: %s."
+             % (med(p_rle) / med(p_png), " ".join("%.3f" % (x / y) for x, y in zip(p_rle, p_png)), same_pass),
+             "* Bytes uploaded per full batch of %d by the staging's one copy: PNG %d (median; descriptors and masks), RLE %d (descriptors,"
+             % (BATCH, med(b_png), med(b_rle)),
+             "  sources and counts; the mask slots exist on the device only).", ""]
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=256)
@@ -318,11 +475,15 @@ def main():
     ap.add_argument("--sweep", type=int, nargs="?", const=19, default=None, metavar="T",
                     help="measure the threshold sweep at T thresholds (default 19) instead; writes profiles/eval_sweep.md")
     ap.add_argument("--boundary", action="store_true", help="measure Boundary IoU instead; writes profiles/boundary_iou.md")
+    ap.add_argument("--decode", action="store_true", help="measure the mask decoders instead; prints the table (profiles/mask_decode.md)")
+    ap.add_argument("--png-pass", action="store_true", help="print the rounds of a validate pass over PNG records, nothing else")
+    ap.add_argument("--tree", default=None, metavar="DIR", help="import cris.pytorch_amd from this checkout (A/B against another commit)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.boundary and a.sweep is not None:
-        raise SystemExit("--boundary and --sweep are separate measurements")
-    a.out = a.out or os.path.join(ROOT, "profiles", "boundary_iou.md" if a.boundary else "eval_throughput.md" if a.sweep is None else "eval_sweep.md")
+    if a.boundary + (a.sweep is not None) + a.decode + a.png_pass > 1:
+        raise SystemExit("--boundary, --sweep, --decode and --png-pass are separate measurements")
+    if not (a.decode or a.png_pass):
+        a.out = a.out or os.path.join(ROOT, "profiles", "boundary_iou.md" if a.boundary else "eval_throughput.md" if a.sweep is None else "eval_sweep.md")
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU (nothing here is measured on the CPU)")
     dev = torch.device("cuda:0")
@@ -335,6 +496,10 @@ def main():
         return sweep_main(a, dev, recs, pipe, runner)
     if a.boundary:
         return boundary_main(a, dev, recs, pipe, runner)
+    if a.decode:
+        return decode_main(a, dev, recs, pipe, runner)
+    if a.png_pass:
+        return png_pass(a, recs, pipe, runner)
 
     # ---- (a) post-processing of one batch of 32 on fixed logits
     img, word, params = pipe(recs[:BATCH])
